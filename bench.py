@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: multi-view reconstruction views/sec of G2VLM-2B-MoT on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the reconstruction hot path over one synthetic 8-view 518x518 scene
@@ -13,9 +13,17 @@ in HBM when the timed region starts.  With N > 1 every rank reconstructs its own
 (replicas, SURVEY.md §8e: "throughput scaling at 2/4/8 GPUs for C3: replicas only"), so
 `scaling` is weak and `value` is the whole-job aggregate.
 
-Rank 0 prints ONE JSON line; `roofline` prices the dominant kernel (MoT flash attention) from
-HIP-event timing of that kernel at the workload's exact shapes; `cpu_baseline` is the CPU
-oracle timed on this host on a bounded sample (N=1 only).
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times K steps and reports the headline
+(`value`, `ms_per_step`).  --full adds the secondary figures: per-step GPU times (`step_ms`),
+`roofline` / `roofline_gemm` (the dominant kernels, MoT flash attention and the gate/up GEMM, from
+HIP events around their launches inside the timed steps), scenes on two streams, greedy decode
+(batch 1, 2, 8), host image preparation and `cpu_baseline` (the CPU oracle timed on this host on a
+bounded sample, N=1 only).
+
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step returned (the
+reconstruct dict) as DIR/<name>.npy in float32; an array of more than DUMP_MAX_ELEMS elements is
+written as its values at a fixed, seeded set of flat indices.  Weights and inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -48,6 +56,30 @@ class _Tok:
 
 
 NEW_TOKEN_IDS = dict(bos_token_id=1, eos_token_id=2, start_of_image=3, end_of_image=4)
+DUMP_MAX_ELEMS = 1 << 21            # per array (8 MiB in float32): the C3 dict holds four 8 x 518 x 518 x 3 maps
+
+
+def dump_outputs(out_dir, pred):
+    """DIR/<name>.npy for every tensor of a step's result dict: float32 (float64 kept), whole up to DUMP_MAX_ELEMS
+    elements, above that the values at DUMP_MAX_ELEMS flat indices drawn once from a generator seeded with 0 (the same
+    indices on every run), in index order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total, sample = 0, {}
+    for name, t in sorted(pred.items()):
+        if not torch.is_tensor(t):
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            if t.numel() not in sample:
+                g = torch.Generator(); g.manual_seed(0)
+                sample[t.numel()] = torch.randperm(t.numel(), generator=g)[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[sample[t.numel()].to(t.device)]
+        t = t.cpu()
+        arr = (t if t.dtype == torch.float64 else t.float()).numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        total += arr.nbytes
+    assert total <= 64 * 10 ** 6, f"--dump-outputs wrote {total} bytes"
 
 
 def flops_per_scene(dims, n, p, t0):
@@ -141,9 +173,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--decode-tokens", type=int, default=128)
-    ap.add_argument("--overlap", type=int, default=2, help="also report (secondary key, outside the timed region) views/s with scenes issued on this many streams; 1 = skip")
+    ap.add_argument("--full", action="store_true",
+                    help="c3: also the secondary figures (per-step times, rooflines, scenes on two streams, decode, host preparation, "
+                         "CPU baseline); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="c3: write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--decode-tokens", type=int, default=128, help="--full: greedy tokens per decode figure; 0 = skip")
+    ap.add_argument("--overlap", type=int, default=2, help="--full: also report (secondary key, outside the timed region) views/s with scenes issued on this many streams; 1 = skip")
     ap.add_argument("--breakdown", action="store_true", help="c5: print a per-stage wall-time breakdown of one step to stderr")
     ap.add_argument("--scenes-per-step", type=int, default=2, help="c5: scenes per rank and step (their greedy decodes run as one batch)")
     ap.add_argument("--workload", choices=["c3", "c4", "c5"], default="c3",
@@ -152,6 +188,10 @@ def main():
                          "interleaved recon + chat, one scene per rank and step: 8-view pointmaps, then chat_with_recon over the "
                          "same 8 views (8 ViT images, 32-token question, 256 greedy tokens) (BASELINE config 5, replicas)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.dump_outputs and a.workload != "c3":
+        ap.error("--dump-outputs: the c3 workload only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -367,41 +407,47 @@ def main():
     gc.collect()
     gc.disable()
     attn_events, gemm_events = [], []
+    events = a.full and rank == 0                       # kernel events (rooflines): --full, rank 0 only (max-over-ranks keeps it honest)
     for i in range(a.warmup):
-        if rank == 0 and i == a.warmup - 1:            # the last warm-up step already carries the event records of the timed steps
-            model.engine.attn_events = attn_events      # two event records per MoT layer; rank 0 only (max-over-ranks keeps it honest)
+        if events and i == a.warmup - 1:                # the last warm-up step already carries the event records of the timed steps
+            model.engine.attn_events = attn_events      # two event records per MoT layer
             model.engine.gemm_events = gemm_events      # and two around its gate/up GEMM
         past, pred = step()
-    if rank == 0:
+    if events:
         model.engine.attn_events = attn_events
         model.engine.gemm_events = gemm_events
         torch.cuda.synchronize()
         attn_events.clear(); gemm_events.clear()        # only the timed steps' records are read below
     barrier()
-    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]    # per-step GPU times (diagnostic key `step_ms`)
+    # per-step GPU times (diagnostic key `step_ms`, --full)
+    step_ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)] if a.full else None
     ms0 = torch.cuda.memory_stats(dev) if os.environ.get("G2V_STEP_DIAG") else None  # tools/step_outliers.py
     t0 = time.perf_counter()
-    step_ev[0].record()
+    if step_ev:
+        step_ev[0].record()
     diag_allocs = []
     for i in range(a.steps):
         past, pred = step()
-        step_ev[i + 1].record()
+        if step_ev:
+            step_ev[i + 1].record()
         if ms0 is not None:
             diag_allocs.append(torch.cuda.memory_stats(dev)["num_device_alloc"] - ms0["num_device_alloc"])
     barrier()
     dt = time.perf_counter() - t0
     gc.enable()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, pred)
     if ms0 is not None:
         ms1 = torch.cuda.memory_stats(dev)
         print("G2V_STEP_DIAG device mallocs in the timed region:", ms1["num_device_alloc"] - ms0["num_device_alloc"], "frees:",
               ms1["num_device_free"] - ms0["num_device_free"], "retries:", ms1["num_alloc_retries"] - ms0["num_alloc_retries"],
               "reserved GB:", round(ms1["reserved_bytes.all.current"] / 2 ** 30, 2), "cumulative by step:", diag_allocs,
               "reserved MB added:", round((ms1["reserved_bytes.all.current"] - ms0["reserved_bytes.all.current"]) / 2 ** 20, 1), file=sys.stderr, flush=True)
-    step_ms = [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(a.steps)]
+    step_ms = [round(step_ev[i].elapsed_time(step_ev[i + 1]), 2) for i in range(a.steps)] if step_ev else None
     model.engine.attn_events = None
     model.engine.gemm_events = None
     overlap_vps = None
-    if a.overlap > 1:
+    if a.full and a.overlap > 1:
         # secondary figure, measured AFTER the timed region and not part of `value`: scenes of consecutive steps issued on
         # `overlap` streams of this process, so one scene's kernel tails and bandwidth-bound passes are filled by the other's
         # MFMA kernels.  Same work per scene; the per-kernel roofline above is taken on the serial steps, where a kernel has
@@ -425,11 +471,21 @@ def main():
 
     if rank == 0:
         fl = flops_per_scene(dims, N_VIEWS, P, T0)
+        L = dims["llm"]
+        tot = T0 + lq
+        out = {
+            "metric": "views/sec (multi-view recon, G2VLM-2B-MoT)", "value": round(views_per_s, 3), "unit": "views/s",
+            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            "config": {"workload": "C3: 8-view 518x518 reconstruction, full depth (24 DINO + 28 MoT + 15 decoder blocks), 1 scene per GPU",
+                       "views_per_scene": N_VIEWS, "Lq": lq, "Lk": tot, "parallelism": f"replicas x{world}"},
+            "tflops_per_scene": round(fl["total"] / 1e12, 2),
+            "achieved_tflops_per_gpu": round(fl["total"] * a.steps / dt / 1e12, 1),
+        }
+    if rank == 0 and a.full:
         # ---- dominant kernel: MoT flash attention (hd 128, GQA 12:2, Lq 10968 x Lk 10976).  HIP events recorded on the
         # launch stream around every one of its launches INSIDE the timed steps above (28 layers x K steps); the text
         # prefill's 8-row launches are left out by shape.  A launch = flash_fwd64_kernel + its split-KV combine.
-        L = dims["llm"]
-        tot = T0 + lq
         durs = [ev[0].elapsed_time(ev[1]) for ev, l_, t_ in attn_events if l_ == lq and t_ == tot]
         assert len(durs) == L["layers"] * a.steps, (len(durs), L["layers"], a.steps)
         k_ms = sum(durs) / len(durs)
@@ -479,23 +535,17 @@ def main():
                 decode_batch[str(B)] = {"tokens_per_s": round(B * a.decode_tokens / dtb, 1),
                                         "ms_per_step": round(dtb / a.decode_tokens * 1e3, 3),
                                         "hbm_gb_per_s_incl_setup": round((w_bytes + B * kv_bytes) * a.decode_tokens / dtb / 1e9, 1)}
-        out = {
-            "metric": "views/sec (multi-view recon, G2VLM-2B-MoT)", "value": round(views_per_s, 3), "unit": "views/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": "C3: 8-view 518x518 reconstruction, full depth (24 DINO + 28 MoT + 15 decoder blocks), 1 scene per GPU",
-                       "views_per_scene": N_VIEWS, "Lq": lq, "Lk": tot, "parallelism": f"replicas x{world}"},
-            "tflops_per_scene": round(fl["total"] / 1e12, 2),
-            "achieved_tflops_per_gpu": round(fl["total"] * a.steps / dt / 1e12, 1),
+        out.update({
             "decode_tokens_per_s": round(tok_s, 1) if tok_s else None, "decode_kv_len": int(tot),
             "views_per_s_scenes_on_two_streams": round(overlap_vps, 2) if overlap_vps else None,
             "step_ms": step_ms, "decode_batch": decode_batch, "decode_roofline": decode_roofline, "roofline_gemm": roofline_gemm,
             "host_prep_ms": host_prep_ms(model, N_VIEWS),
             "host_prep_note": "per 8-view scene, NOT in `value`: pinned upload of 8 decoded 1280x720 uint8 frames + device LANCZOS resize to 518 wide (bit-exact with Pillow) + device normalise; image file decoding not included (no files offline)",
             "roofline": roofline,
-        }
+        })
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dims)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -8,7 +8,7 @@ if __name__ == "__main__":
     steps = sys.argv[1] if len(sys.argv) > 1 else "40"
     env = dict(os.environ, G2V_STEP_DIAG="1")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--decode-tokens", "0", "--overlap", "1", "--steps", steps],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--decode-tokens", "0", "--overlap", "1", "--steps", steps],
                        capture_output=True, text=True, env=env)
     import json
     d = json.loads(r.stdout.strip().splitlines()[-1])
