@@ -72,6 +72,25 @@ def rope2d_tables(D, seq_len, base=100.0):
     return freqs.cos(), freqs.sin()
 
 
+def attn_tile_rows(windows, Hq):
+    """Query rows per attention item (128: 4-wave workgroups, 256: 8-wave) of the plan Engine.plan builds for `windows`
+    (q0, q_len, k0, k_len, causal[, phase]) with Hq query heads."""
+    # long KV ranges (MoT global attention, ViT): 8-wave / 256-row workgroups share each K/V tile between twice
+    # the queries (0.93 vs 0.82 PF at C3); short per-view windows keep the 4-wave form
+    # ... when there are enough query rows to make 256-row items worth it: a 731-row ViT prefill or a long text
+    # prompt against a 15 k-row cache runs 3-6 % faster on 128-row tiles (tools/attn_small_q.py)
+    long_kv = sum(w[3] for w in windows if w[0] == windows[0][0]) >= 2048 and max(w[1] for w in windows) >= 2048
+    # per-view windows (DINO, the Pi3 decoders): 256-row items are 5-8 % faster there too (tools/attn_windows.py: 118 ->
+    # 109 us, 150 -> 142 us at 8 x 1369) as long as the last, partly filled tile does not eat the gain and there are
+    # enough items to fill the chip twice over
+    tall = False
+    if not long_kv:
+        pad = lambda t: sum((w[1] + t - 1) // t * t for w in windows) / max(1, sum(w[1] for w in windows))  # noqa: E731
+        items = sum((w[1] + 255) // 256 for w in windows) * Hq
+        tall = items >= 512 and pad(256) <= 1.12 * pad(128)
+    return 256 if (long_kv or tall) else 128
+
+
 class Engine:
     def __init__(self, weights, dims):
         self.w = weights
@@ -108,20 +127,7 @@ class Engine:
     def plan(self, windows, Hq):
         key = (tuple(windows), Hq)
         if key not in self._tiles:
-            # long KV ranges (MoT global attention, ViT): 8-wave / 256-row workgroups share each K/V tile between twice
-            # the queries (0.93 vs 0.82 PF at C3); short per-view windows keep the 4-wave form
-            # ... when there are enough query rows to make 256-row items worth it: a 731-row ViT prefill or a long text
-            # prompt against a 15 k-row cache runs 3-6 % faster on 128-row tiles (tools/attn_small_q.py)
-            long_kv = sum(w[3] for w in windows if w[0] == windows[0][0]) >= 2048 and max(w[1] for w in windows) >= 2048
-            # per-view windows (DINO, the Pi3 decoders): 256-row items are 5-8 % faster there too (tools/attn_windows.py: 118 ->
-            # 109 us, 150 -> 142 us at 8 x 1369) as long as the last, partly filled tile does not eat the gain and there are
-            # enough items to fill the chip twice over
-            tall = False
-            if not long_kv:
-                pad = lambda t: sum((w[1] + t - 1) // t * t for w in windows) / max(1, sum(w[1] for w in windows))  # noqa: E731
-                items = sum((w[1] + 255) // 256 for w in windows) * Hq
-                tall = items >= 512 and pad(256) <= 1.12 * pad(128)
-            self._tiles[key] = hip.make_attn_plan(windows, Hq, self.dev, tile_rows=256 if (long_kv or tall) else 128)
+            self._tiles[key] = hip.make_attn_plan(windows, Hq, self.dev, tile_rows=attn_tile_rows(windows, Hq))
         return self._tiles[key]
 
     def rope2d_tab(self, D, gh, gw):

@@ -308,6 +308,7 @@ def _decode_plan(plan):
     ([(0, 731, 0, 15000, False)], 12, 128, None),                         # ViT-token prefill: fewer items than workgroups
     ([(0, 300, 0, 900, True)], 4, 128, 7),                                # causal: unequal items, stream-K cuts
     ([(0, 40, 0, 300, True), (40, 200, 300, 200, False)], 2, 128, 5),
+    ([(i * 1369, 1369, i * 1369, 1369, False) for i in range(8)], 16, 256, None),   # DINO windows as C3 runs them (engine.attn_tile_rows)
 ])
 def test_attention_plan_covers_every_kv_tile_once_and_balances(windows, Hq, tile_rows, max_blocks):
     """make_attn_plan: every (descriptor, head) item's 64-key tiles are covered exactly once by the segments; a segment
@@ -353,6 +354,36 @@ def test_attention_plan_covers_every_kv_tile_once_and_balances(windows, Hq, tile
         assert load.max() <= 1.03 * load.mean() + 1, (load.max(), load.mean())     # long equal items: balanced within 3 %
     if windows == [(0, 10968, 0, 10976, False)]:
         assert plan.n_slots <= 160, plan.n_slots             # the first form of the schedule left 512 partial slots here
+
+
+_P3, _P2, _SV, _C4 = 1369, 777, 731, (5484, 43880)
+_CALL_SITES = [
+    ("DINO C3", [(i * _P3, _P3, i * _P3, _P3, False) for i in range(8)], 16, 256),
+    ("DINO C2", [(i * _P2, _P2, i * _P2, _P2, False) for i in range(2)], 16, 128),
+    ("decoder self C3", [(i * _P3, _P3, i * _P3, _P3, False) for i in range(8)], 16, 256),
+    ("decoder self C2", [(i * _P2, _P2, i * _P2, _P2, False) for i in range(2)], 16, 128),
+    ("decoder cross C3", [(i * _P3, _P3, 0, _P3, False) for i in range(8)], 16, 256),
+    ("decoder cross C2", [(i * _P2, _P2, 0, _P2, False) for i in range(2)], 16, 128),
+    ("ViT 1 image", [(0, 2916, 0, 2916, False)], 16, 256),
+    ("ViT 8 images", [(i * 2916, 2916, i * 2916, 2916, False) for i in range(8)], 16, 256),
+    ("MoT C3", [(0, 10968, 0, 10976, False)], 12, 256),
+    ("MoT C2", [(0, 1558, 0, 1566, False)], 12, 128),
+    ("MoT text after prefix", [(0, 40, 0, 11016, True)], 12, 128),
+    ("MoT ViT staircase", [(j * _SV, _SV, 0, 11000 + (j + 1) * _SV, False) for j in range(8)], 12, 128),
+    ("C4 first rank", [(0, _C4[0], 0, _C4[0], False, 0), (0, _C4[0], _C4[0], _C4[1] - _C4[0], False, 1)], 12, 256),
+    ("C4 middle rank", [(0, _C4[0], 16460, _C4[0], False, 0), (0, _C4[0], 0, 16460, False, 1),
+                        (0, _C4[0], 16460 + _C4[0], _C4[1] - 16460 - _C4[0], False, 1)], 12, 256),
+    ("C4 last rank", [(0, _C4[0], _C4[1] - _C4[0], _C4[0], False, 0), (0, _C4[0], 0, _C4[1] - _C4[0], False, 1)], 12, 256),
+]
+
+
+@pytest.mark.parametrize("site,windows,Hq,rows", [pytest.param(*c, id=c[0]) for c in _CALL_SITES])
+def test_attn_tile_rows_at_the_call_sites(site, windows, Hq, rows):
+    """engine.attn_tile_rows at the real shapes of every attention call site: 256-row items run flash_fwd_kernel<D, 8> (or
+    flash_fwd64_kernel for D = 128 with ldk == ldv), 128-row items flash_fwd_kernel<D, 4>.  tests/test_attention_gpu.py checks
+    each of these forms at its call site's layout; a retuned rule that moves a call site to another form must update both."""
+    from g2vlm_amd.engine import attn_tile_rows
+    assert attn_tile_rows(tuple(windows), Hq) == rows, site
 
 
 def test_attention_plan_phases_share_output_tiles():
