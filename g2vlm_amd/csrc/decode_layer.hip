@@ -201,60 +201,6 @@ __global__ __launch_bounds__(256, 2) void decode_attn_pg_kernel(AttnArgs a G2V_S
   decode_attn_pg_body<false, false, 4>(a, lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, threadIdx.x G2V_STAMP_PASS_DEV);
 }
 
-// out[z][h][d] = sum_b O_b e^(m_b - M) / sum_b l_b e^(m_b - M) over the NBH <= 128 block partials of a head.
-// grid (Hq, scenes); 1024 threads = 128 d x 8 groups of 16 consecutive partials.  All loads of a thread - the (m, l) pair
-// of partial `tid` and its 16 O words - are issued before the first use (one memory round trip; a loop of dependent loads
-// over the partials made this kernel 11.7 us, as long as the attention itself); reductions by DPP / readlane, the 16 weights
-// of a group by four 16-byte LDS reads.
-__device__ __forceinline__ float row16_max(float x) {
-  x = fmaxf(x, dpp_f<0x128>(x)); x = fmaxf(x, dpp_f<0x124>(x)); x = fmaxf(x, dpp_f<0x122>(x)); x = fmaxf(x, dpp_f<0x121>(x));
-  return x;
-}
-
-__global__ __launch_bounds__(1024) void decode_combine_pg_kernel(const float* ws, __bf16* out, int NBH) {
-  __shared__ float sm[2];
-  __shared__ __attribute__((aligned(16))) float sf[128];
-  __shared__ float sL[2], sO[8][128];
-  const int h = blockIdx.x, z = blockIdx.y, tid = threadIdx.x, d = tid & 127, g = tid >> 7;
-  const float* p = ws + ((size_t)z * gridDim.x + h) * NBH * 130;
-  float ov[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) ov[k] = p[min(16 * g + k, NBH - 1) * 130 + 2 + d];
-  float m = -INFINITY, l = 0.f;
-  if (tid < NBH) { m = p[tid * 130]; l = p[tid * 130 + 1]; }
-  if (tid < 128) {                                          // waves 0 and 1 hold the (m, l) pairs
-    float mx = row16_max(m);
-    mx = fmaxf(fmaxf(readlane_f(mx, 0), readlane_f(mx, 16)), fmaxf(readlane_f(mx, 32), readlane_f(mx, 48)));
-    if ((tid & 63) == 0) sm[tid >> 6] = mx;
-  }
-  __syncthreads();
-  const float M = fmaxf(sm[0], sm[1]);
-  if (tid < 128) {
-    const float f = m == -INFINITY ? 0.f : __expf(m - M);
-    sf[tid] = f;
-    const float lw = wave_sum_dpp(l * f);
-    if ((tid & 63) == 0) sL[tid >> 6] = lw;
-  }
-  __syncthreads();
-  float O = 0.f;
-#pragma unroll
-  for (int k4 = 0; k4 < 4; ++k4) {
-    const f32x4 f4 = *reinterpret_cast<const f32x4*>(&sf[16 * g + 4 * k4]);
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      if (16 * g + 4 * k4 + e < NBH) O = fmaf(ov[4 * k4 + e], f4[e], O);
-  }
-  sO[g][d] = O;
-  __syncthreads();
-  if (g == 0) {
-    const float Lt = sL[0] + sL[1];
-    float Ot = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) Ot += sO[k][d];
-    out[((size_t)z * gridDim.x + h) * 128 + d] = f2bf(Ot / Lt);
-  }
-}
-
 template <int XMODE, bool ACT, int KCH>
 int gemv_pg_launch_rb(int rb, int blocks, int threads, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W,
                       const __bf16* bias, __bf16* out, float* res, int N, int K) {

@@ -621,19 +621,25 @@ class Engine:
         hp.gather_rows(w["embed"], st["tok"], x)
         hp.mrope_table_into(st["pos"], w["inv_freq"], st["cos"], st["sin"])
         pgb = B <= 8 and st["attn_pg"]      # the persistent-grid GEMVs with B rows per weight pass (csrc/decode_batch.hip)
+        pre = st.get("prefix")              # decode_begin_shared: every slot's cache is this prefix + its own suffix block
         for i in range(Lc["layers"]):
             p = f"L{i}.und."
             if pgb:
                 hp.gemv_pg_batch(x, w[p + "qkv.w"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"])
-                hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
-                                  st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
+                if pre is not None:
+                    self._shared_attn(st, pre, i)
+                else:
+                    hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
+                                      st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
                 hp.gemv_pg_batch(st["ao"], w[p + "o.w"], res=x)
                 hp.gemv_pg_batch(x, w[p + "gu.w"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
                 hp.gemv_pg_batch(st["act"], w[p + "down.w"], res=x)
                 continue
             hp.rmsnorm(x, w[p + "ln1"], w[p + "ln1"], 0, eps, out=h)
             hp.linear(h, w[p + "qkv.w"], w[p + "qkv.b"], hp.EPI_BF16, out=st["qkv"], ws=st["gws"])
-            if st["attn_pg"]:
+            if pre is not None:
+                self._shared_attn(st, pre, i)
+            elif st["attn_pg"]:
                 hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
                                   st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
             elif st["fused_attn"]:
@@ -691,19 +697,24 @@ class Engine:
         if sample is not None:                               # (seed, temperature): draw instead of argmax, every slot its own stream
             st["rng"] = hip.make_rng(sample[0], sample[1], d)
         if use_graph:
-            init = {n: st[n].clone() for n in ("pos", "row", "len", "tok") + (("rng",) if sample is not None else ())}
-            s = torch.cuda.Stream(device=d)
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self._decode_batch_body(st)                  # lazy module loads must not happen during capture
-            torch.cuda.current_stream().wait_stream(s)
-            for n, t in init.items():
-                st[n].copy_(t)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                self._decode_batch_body(st)
-            st["graph"] = g
+            self._capture_batch(st)
         return st
+
+    def _capture_batch(self, st):
+        """Capture the batched step of `st` into st["graph"] (after one warm-up step whose state changes are undone)."""
+        d = self.dev
+        init = {n: st[n].clone() for n in ("pos", "row", "len", "tok") + (("rng",) if st.get("rng") is not None else ())}
+        s = torch.cuda.Stream(device=d)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            self._decode_batch_body(st)                      # lazy module loads must not happen during capture
+        torch.cuda.current_stream().wait_stream(s)
+        for n, t in init.items():
+            st[n].copy_(t)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._decode_batch_body(st)
+        st["graph"] = g
 
     def decode_set_slot(self, st, j, cache, start_token, position, max_new_tokens):
         """Put a prefilled scene into slot j: copy its cache rows into the slot's block and point the slot's device-side
@@ -735,6 +746,39 @@ class Engine:
         st = self.decode_open_slots(B, max(c.length for c in caches) + max_new_tokens + 1, use_graph, sample)
         for j, c in enumerate(caches):
             self.decode_set_slot(st, j, c, start_tokens[j], positions[j], max_new_tokens)
+        return st
+
+    # ------------------------------------------------------------------ shared-prefix decode (several questions, one scene)
+    def _shared_attn(self, st, pre, i):
+        w, Lc = self.w, self.dims["llm"]
+        p = f"L{i}.und."
+        hip.decode_attn_shared(st["qkv"], w[p + "qn"], w[p + "kn"], Lc["eps"], 1, st["cos"], st["sin"], pre.k[i], pre.v[i],
+                               st["prefix_len"], st["k"][i], st["v"][i], st["len"], st["cap"], st["cap"], Lc["heads"], Lc["kv_heads"],
+                               128 ** -0.5, st["ao"], st["ws3"])
+
+    def decode_begin_shared(self, prefix_cache, suffixes, start_tokens, positions, max_new_tokens, use_graph=True, sample=None):
+        """Batched decode of B questions about one scene.  prefix_cache: the KVCache of the shared rows (system prompt,
+        views), read in place and never written; suffixes[j]: a KVCache holding question j's own prefilled rows (the rows
+        that follow the prefix in its single-question cache); start_tokens / positions: one int per question.
+        The state is decode_open_slots' with [B, cap_s, Hkv, 128] suffix blocks (cap_s: the longest question plus
+        max_new_tokens + 1) in place of whole-scene blocks; the attention (g2v_decode_attn_shared) reads the prefix once
+        per step for all questions.  Nothing allocated here depends on the prefix length.  The captured graph holds
+        pointers into prefix_cache: it must not be reallocated while this state decodes."""
+        B = len(suffixes)
+        if not (1 <= B <= 64) or len(start_tokens) != B or len(positions) != B:
+            raise ValueError("decode_begin_shared: 1..64 questions, one start token and one position each")
+        plen = prefix_cache.length
+        if plen < 1:
+            raise ValueError("decode_begin_shared: empty prefix")
+        Lc = self.dims["llm"]
+        st = self.decode_open_slots(B, max(c.length for c in suffixes) + max_new_tokens + 1, use_graph=False, sample=sample)
+        st["prefix"], st["prefix_len"] = prefix_cache, plen
+        st["ws3"] = torch.empty(hip.decode_attn_shared_workspace(Lc["heads"], Lc["kv_heads"], B, plen, st["cap"]) // 4,
+                                dtype=torch.float32, device=self.dev)
+        for j, c in enumerate(suffixes):
+            self.decode_set_slot(st, j, c, start_tokens[j], positions[j], max_new_tokens)
+        if use_graph:
+            self._capture_batch(st)
         return st
 
     def decode_step_batch(self, st):

@@ -89,6 +89,8 @@ _SIGS = {
     "g2v_decode_attn_pg_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_decode_attn_pg": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P], C.c_int),
     "g2v_sample_rows_bf16": ([_P, _I, _I, _L, _P, _P, _P, _P], C.c_int),
+    "g2v_decode_attn_shared_workspace": ([_I, _I, _I, _I, _I], C.c_int64),
+    "g2v_decode_attn_shared": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -661,6 +663,22 @@ def decode_attn_pg(qkv, qw, kw, eps, und_rounding, cos, sin, k_cache, v_cache, o
     _ck(lib().g2v_decode_attn_pg(_p(qkv), _p(qw), _p(kw), eps, int(und_rounding), _p(cos), _p(sin), _p(k_cache), _p(v_cache), _p(out),
                                  _p(len_dev), qkv.shape[0], int(scene_rows), int(max_len), Hq, Hkv, scale, _p(workspace), _stream()),
         "g2v_decode_attn_pg")
+    return out
+
+
+def decode_attn_shared_workspace(Hq, Hkv, batch, prefix_len, suffix_max_len):
+    return int(lib().g2v_decode_attn_shared_workspace(Hq, Hkv, batch, prefix_len, suffix_max_len))
+
+
+def decode_attn_shared(qkv, qw, kw, eps, und_rounding, cos, sin, k_prefix, v_prefix, prefix_len, k_suffix, v_suffix, suffix_len_dev,
+                       suffix_rows, suffix_max_len, Hq, Hkv, scale, out, workspace):
+    """g2v_decode_attn_shared: decode_attn_pg for B slots over one shared, read-only prefix [0, prefix_len) of
+    k_prefix / v_prefix plus a suffix block per slot (k_suffix / v_suffix [B, suffix_rows, Hkv, 128], lengths on the device,
+    the new token included); the prefix rows are read once per column group of slots, not once per slot."""
+    _ck(lib().g2v_decode_attn_shared(_p(qkv), _p(qw), _p(kw), eps, int(und_rounding), _p(cos), _p(sin), _p(k_prefix), _p(v_prefix),
+                                     int(prefix_len), _p(k_suffix), _p(v_suffix), _p(suffix_len_dev), qkv.shape[0], int(suffix_rows),
+                                     int(suffix_max_len), Hq, Hkv, scale, _p(out), _p(workspace), _stream()),
+        "g2v_decode_attn_shared")
     return out
 
 

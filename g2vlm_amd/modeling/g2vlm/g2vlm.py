@@ -457,18 +457,28 @@ class G2VLM:
     def _chat_prefill(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt):
         """The cache-building half of chat_with_recon (reference g2vlm.py:1305-1398): system prompt, geometry views,
         ViT views, question.  Returns the filled cache and the start-token inputs of generate_text."""
+        past, newlens, new_rope = self._chat_geometry(tokenizer, new_token_ids, dino_image_transform, images)
+        return self._chat_suffix(past, newlens, new_rope, tokenizer, new_token_ids, image_transform, images, prompt)
+
+    def _chat_geometry(self, tokenizer, new_token_ids, dino_image_transform, images):
+        """System prompt and geometry views (reference g2vlm.py:1305-1358): a new cache and its (lens, rope) after them."""
         past = NaiveCache(self.dims["llm"]["layers"], self.dims["llm"]["kv_heads"], self.device)
         sys_p = "<|im_start|>system\nYou are a helpful assistant.<|im_end|>\n<|im_start|>user\n"
         gi_text, newlens, new_rope = self.prepare_prompts_pure_text([0], [0], [sys_p], tokenizer, new_token_ids)
         gi, newlens, new_rope = self.prepare_dino_images_pi3(newlens, new_rope, list(images) if not torch.is_tensor(images) else images,
                                                              dino_image_transform, new_token_ids)
         past, _ = self.prefill_text_and_dino(past, gi_text, gi)      # the system prompt under the DINO encoder
-        return self._chat_suffix(past, newlens, new_rope, tokenizer, new_token_ids, image_transform, images, prompt)
+        return past, newlens, new_rope
 
     def _chat_suffix(self, past, newlens, new_rope, tokenizer, new_token_ids, image_transform, images, prompt):
         """The stages of chat_with_recon after the geometry views (reference g2vlm.py:1360-1398): one ViT stage per image, then
         the question.  Split out because the view-sharded prefill (g2vlm_amd/sharded.py::chat_view_sharded) builds the
         geometry rows of `past` on several ranks and continues here on one."""
+        past, newlens, new_rope = self._chat_vit(past, newlens, new_rope, new_token_ids, image_transform, images)
+        return self._chat_question(past, newlens, new_rope, tokenizer, new_token_ids, prompt)
+
+    def _chat_vit(self, past, newlens, new_rope, new_token_ids, image_transform, images):
+        """The ViT stages of chat_with_recon (reference g2vlm.py:1360-1370), one per image: the cache and its (lens, rope)."""
         gis = []
         for image in (images if not torch.is_tensor(images) else [None] * images.shape[0]):
             gi, newlens, new_rope = self.prepare_vit_images(newlens, new_rope, [image], image_transform, new_token_ids)
@@ -479,6 +489,11 @@ class G2VLM:
                 past = self._flush_vit(past, gis)              # another patch grid: close the run of equal-grid images
             gis.append(gi)
         past = self._flush_vit(past, gis)
+        return past, newlens, new_rope
+
+    def _chat_question(self, past, newlens, new_rope, tokenizer, new_token_ids, prompt):
+        """The question stage of chat_with_recon (reference g2vlm.py:1372-1398): its rows appended to `past`, and the
+        start-token inputs of generate_text."""
         gi, newlens, new_rope = self.prepare_prompts_pure_text(newlens, new_rope, [prompt + "<|im_end|>\n<|im_start|>assistant"],
                                                                tokenizer, new_token_ids)
         past = self.forward_cache_update_text(past, **gi)
@@ -586,4 +601,65 @@ class G2VLM:
             pasts.append(past); starts.append(gi)
         ids = self.generate_text_batch(pasts, starts, max_length, end_token_id=new_token_ids["eos_token_id"], do_sample=do_sample,
                                        temperature=temperature)
+        return [tokenizer.decode(i[1:, 0]) for i in ids]
+
+    # ---- several questions about one scene: one prefill of the scene, its cache rows shared by every question's decode
+    @torch.no_grad()
+    def generate_text_shared(self, past_key_values, questions, max_length, end_token_id=None, do_sample=False, temperature=1.0):
+        """generate_text_batch for B questions whose caches share their first rows.  past_key_values: the KVCache of the
+        shared rows; questions[j] = (suffix, start_inputs): `suffix` a KVCache holding question j's own rows (those that
+        follow the shared ones in its single-question cache), `start_inputs` what generate_text would be given for that
+        cache.  The decode reads the shared rows in place, once per step for all questions (g2v_decode_attn_shared), and
+        never writes them: on return past_key_values has the same length and the same bits, and more questions can be
+        asked on it.  Returns a list of B LongTensors [n_j, 1], each cut at its first end_token_id as generate_text does."""
+        eng = self.engine
+        B = len(questions)
+        if not 1 <= B <= 64:
+            raise ValueError("generate_text_shared: 1..64 questions")
+        plen = past_key_values.length
+        starts, poss = [], []
+        for suf, gi in questions:
+            assert plen + suf.length == int(_cpu(gi["key_values_lens"]).sum())
+            starts.append(int(_cpu(gi["packed_start_tokens"])[0]))
+            poss.append(int(_cpu(gi["packed_query_position_ids"])[0, 0]))
+        st = eng.decode_begin_shared(past_key_values, [q[0] for q in questions], starts, poss, max_length,
+                                     use_graph=self.use_decode_graph, sample=self._sample_arg(do_sample, temperature))
+        out = self._greedy_loop(lambda: eng.decode_step_batch(st), st["tok"], B, max_length, end_token_id)
+        return [torch.tensor(o, dtype=torch.long).view(-1, 1) for o in out]
+
+    @torch.no_grad()
+    def prefill_questions(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompts):
+        """The cache-building half of chat_with_recon_questions: the scene once, then every question's rows on top of it
+        (the single-question path's kernels and bits), moved into a cache of their own.  Returns (scene cache,
+        [(question cache, start inputs)]) as generate_text_shared takes them."""
+        past, newlens, new_rope = self._chat_geometry(tokenizer, new_token_ids, dino_image_transform, images)
+        past, newlens, new_rope = self._chat_vit(past, newlens, new_rope, new_token_ids, image_transform, images)
+        plen = past.length
+        questions = []
+        for prompt in prompts:
+            past, gi = self._chat_question(past, newlens, new_rope, tokenizer, new_token_ids, prompt)
+            n = past.length - plen
+            suf = NaiveCache(past.num_layers, past.hkv, self.device, capacity=n)
+            for i in range(past.num_layers):
+                suf.k[i].copy_(past.k[i][plen:plen + n]); suf.v[i].copy_(past.v[i][plen:plen + n])
+            suf.length = n
+            past.length = plen                            # the next question goes where this one went
+            questions.append((suf, gi))
+        return past, questions
+
+    @torch.no_grad()
+    def chat_with_recon_questions(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompts, max_length,
+                                  do_sample=False, temperature=1.0):
+        """chat_with_recon for several questions about the same views: the scene (system prompt, geometry views, ViT
+        images) is prefilled once; each question's rows are prefilled on top of it exactly as chat_with_recon does, moved
+        into a cache of their own, and the scene's cache is set back to its length; then all questions decode together over
+        the one copy of the scene's rows (generate_text_shared).  Returns one answer per prompt."""
+        prompts = list(prompts)
+        if not 1 <= len(prompts) <= 64:
+            raise ValueError("chat_with_recon_questions: 1..64 prompts")
+        if do_sample and not float(temperature) > 0:
+            raise ValueError("temperature must be > 0 when do_sample=True")       # before the prefill, not after it
+        past, questions = self.prefill_questions(tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompts)
+        ids = self.generate_text_shared(past, questions, max_length, end_token_id=new_token_ids["eos_token_id"], do_sample=do_sample,
+                                        temperature=temperature)
         return [tokenizer.decode(i[1:, 0]) for i in ids]

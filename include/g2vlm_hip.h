@@ -301,6 +301,22 @@ int64_t g2v_decode_attn_pg_workspace(int Hq, int Hkv, int batch);
 int g2v_decode_attn_pg(const void* qkv, const void* q_norm_w, const void* k_norm_w, float eps, int und_rounding,
                        const void* cos, const void* sin, void* k_cache, void* v_cache, void* out, const void* Lk_dev,
                        int batch, int64_t scene_rows, int max_len, int Hq, int Hkv, float scale, void* workspace, void* stream);
+
+/* ---- shared-prefix decode (csrc/decode_shared.hip): B questions about one scene ----------------------------------------
+ * One step of g2v_decode_attn_pg for `batch` query slots whose caches share their first rows: slot z attends to the prefix
+ * rows [0, prefix_len) of k_prefix / v_prefix [>= prefix_len, Hkv, 128] (read only, fetched once per column group of
+ * floor(32 / G) slots rather than once per slot) followed by its own suffix rows [0, suffix_len_dev[z]) of
+ * k_suffix / v_suffix [batch, suffix_rows, Hkv, 128].  suffix_len_dev (int32 [batch], on the device) INCLUDES the new token:
+ * its normalised, rotated K row and its V row go to suffix row suffix_len_dev[z] - 1 of slot z, bit-identical to what
+ * g2v_decode_attn_pg appends.  qkv [batch, (Hq + 2 Hkv) * 128] raw fused rows, cos / sin [batch, 128], out [batch, Hq * 128]:
+ * as g2v_decode_attn_pg, whose result on the concatenated cache this is up to fp32 summation order.  Rows past prefix_len
+ * or past a suffix length may hold anything.  batch 1..64, prefix_len >= 1, suffix_rows >= suffix_max_len >= every suffix
+ * length; hipGraph-capturable.  workspace >= g2v_decode_attn_shared_workspace(...) bytes (0: invalid shape).            */
+int64_t g2v_decode_attn_shared_workspace(int Hq, int Hkv, int batch, int prefix_len, int suffix_max_len);
+int g2v_decode_attn_shared(const void* qkv, const void* q_norm_w, const void* k_norm_w, float eps, int und_rounding,
+                           const void* cos, const void* sin, const void* k_prefix, const void* v_prefix, int prefix_len,
+                           void* k_suffix, void* v_suffix, const void* suffix_len_dev, int batch, int64_t suffix_rows,
+                           int suffix_max_len, int Hq, int Hkv, float scale, void* out, void* workspace, void* stream);
 #ifdef __cplusplus
 }
 #endif
