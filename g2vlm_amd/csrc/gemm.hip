@@ -312,29 +312,56 @@ int launch_bf16(const GemmArgs& a, int total_tiles, hipStream_t s) {
 
 }  // namespace
 
-extern "C" int g2v_gemm_bf16(const g2v_gemm_desc* d, void* stream) {
+// The one place that decides which kernel serves a descriptor: g2v_gemm_bf16 launches what it picks, g2v_gemm_route
+// reports it.  r = {form, tile height, in-workgroup K split S, cross-workgroup K split KS}; G2V_ERR_ARG for a bad descriptor.
+enum { FORM_128 = 1, FORM_BIG = 2, FORM_8P = 3, FORM_4W = 4, FORM_SKINNY = 5 };
+
+static int gemm_route(const g2v_gemm_desc* d, int32_t r[4]) {
   if (!d || d->ngroups < 1 || d->ngroups > 2 || d->N <= 0 || d->K <= 0 || (d->K & 7) || (d->lda & 7)) return G2V_ERR_ARG;
   if (d->epilogue == G2V_EPI_SWIGLU && (d->N & 31)) return G2V_ERR_ARG;
+  for (int i = 0; i < d->ngroups; ++i)
+    if (d->g[i].M < 0 || !d->g[i].W || !d->g[i].C || (d->g[i].M > 0 && !d->g[i].A)) return G2V_ERR_ARG;
+  const bool res_bf16 = d->epilogue == G2V_EPI_RES_BF16;
+  r[2] = r[3] = 1;
   const int force = d->flags & (G2V_GEMM_FORCE_SMALL_TILE | G2V_GEMM_FORCE_BIG_TILE | G2V_GEMM_FORCE_8P);
   if (force == 0 && g2v_gemm_skinny_eligible(d)) {
-    for (int i = 0; i < d->ngroups; ++i)
-      if (d->g[i].M < 0 || !d->g[i].W || !d->g[i].C || (d->g[i].M > 0 && !d->g[i].A)) return G2V_ERR_ARG;
-    if (d->epilogue == G2V_EPI_RES_BF16)
-      for (int i = 0; i < d->ngroups; ++i) if (d->g[i].M > 0 && !d->g[i].res) return G2V_ERR_ARG;
-    return g2v_gemm_skinny_launch(d, (hipStream_t)stream);
+    int M = 0;
+    for (int i = 0; i < d->ngroups; ++i) {
+      if (res_bf16 && d->g[i].M > 0 && !d->g[i].res) return G2V_ERR_ARG;
+      if (d->g[i].M > 0) M = d->g[i].M;
+    }
+    r[0] = FORM_SKINNY; r[1] = M <= 16 ? 16 : (M <= 32 ? 32 : 64);
+    g2v_gemm_skinny_split(d, M, &r[2], &r[3]);
+    return G2V_OK;
   }
   if (g2v_gemm_8p_supported(d) && (force == G2V_GEMM_FORCE_8P || (force == 0 && g2v_gemm_8p_preferred(d)))) {
-    for (int i = 0; i < d->ngroups; ++i)
-      if (d->g[i].M < 0 || !d->g[i].W || !d->g[i].C || (d->g[i].M > 0 && !d->g[i].A)) return G2V_ERR_ARG;
-    if (d->epilogue == G2V_EPI_RES_BF16)
+    if (res_bf16)
       for (int i = 0; i < d->ngroups; ++i) if (!d->g[i].res) return G2V_ERR_ARG;
-    return g2v_gemm_8p_launch(d, (hipStream_t)stream);
+    r[0] = g2v_gemm_8p_four_waves(d) ? FORM_4W : FORM_8P; r[1] = g2v_gemm_8p_height(d);
+    return G2V_OK;
   }
   if (!(d->flags & G2V_GEMM_FORCE_SMALL_TILE) && ((d->flags & G2V_GEMM_FORCE_BIG_TILE) ? (d->K % 64 == 0 && d->N % 256 == 0) : g2v_gemm_big_eligible(d))) {
-    for (int i = 0; i < d->ngroups; ++i)
-      if (d->g[i].M < 0 || !d->g[i].W || !d->g[i].C || (d->g[i].M > 0 && !d->g[i].A)) return G2V_ERR_ARG;
-    return g2v_gemm_big_launch(d, (hipStream_t)stream);
+    r[0] = FORM_BIG; r[1] = g2v_gemm_big_height(d);
+    return G2V_OK;
   }
+  if (res_bf16)
+    for (int i = 0; i < d->ngroups; ++i) if (!d->g[i].res) return G2V_ERR_ARG;
+  r[0] = FORM_128; r[1] = BM;
+  return G2V_OK;
+}
+
+extern "C" int g2v_gemm_route(const g2v_gemm_desc* d, int32_t out[4]) {
+  if (!out) return G2V_ERR_ARG;
+  return gemm_route(d, out);
+}
+
+extern "C" int g2v_gemm_bf16(const g2v_gemm_desc* d, void* stream) {
+  int32_t r[4];
+  const int rc = gemm_route(d, r);
+  if (rc != G2V_OK) return rc;
+  if (r[0] == FORM_SKINNY) return g2v_gemm_skinny_launch(d, (hipStream_t)stream);
+  if (r[0] == FORM_8P || r[0] == FORM_4W) return g2v_gemm_8p_launch(d, (hipStream_t)stream);
+  if (r[0] == FORM_BIG) return g2v_gemm_big_launch(d, (hipStream_t)stream);
   GemmArgs a;
   a.ngroups = d->ngroups; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
   a.tiles_n = (d->N + BN - 1) / BN; a.flags = d->flags;
@@ -344,11 +371,7 @@ extern "C" int g2v_gemm_bf16(const g2v_gemm_desc* d, void* stream) {
     GemmGroup& g = a.g[i];
     g.A = (const __bf16*)s.A; g.W = (const __bf16*)s.W; g.bias = (const __bf16*)s.bias; g.C = s.C;
     g.res = s.res; g.gamma = (const float*)s.gamma; g.M = s.M; g.tile_start = total;
-    if (i < d->ngroups) {
-      if (s.M < 0 || !s.W || !s.C || (s.M > 0 && !s.A)) return G2V_ERR_ARG;
-      if (d->epilogue == G2V_EPI_RES_BF16 && !s.res) return G2V_ERR_ARG;
-      total += ((s.M + BM - 1) / BM) * a.tiles_n;
-    }
+    if (i < d->ngroups) total += ((s.M + BM - 1) / BM) * a.tiles_n;
   }
   a.sm = 1; a.sn = 1;
   // 96 resident tiles per XCD (3 blocks x 32 CUs): +3..8 % over row-major order on the C3 shapes (profiles/)

@@ -593,7 +593,9 @@ int launch(const P8Args& a, int bm, int total, hipStream_t s) {
   if (a.flags & G2V_GEMM_8P_TWO_BARRIER) {                                    // A/B: the two-barrier loop in lockstep
     if (bm == 288) return launch_h<EPI, 5, 4, 0>(a, total, s);
     if (bm == 256) return launch_h<EPI, 4, 4, 0>(a, total, s);
+    if (bm == 224) return launch_h<EPI, 4, 3, 0>(a, total, s);
     if (bm == 192) return launch_h<EPI, 4, 2, 0>(a, total, s);
+    if (bm == 160) return launch_h<EPI, 3, 2, 0>(a, total, s);
     return launch_h<EPI, 2, 2, 0>(a, total, s);
   }
   if (a.flags & G2V_GEMM_8P_PIPELINED) {                                      // A/B: round 1's default (one barrier per phase)
@@ -647,18 +649,12 @@ bool g2v_gemm_8p_preferred(const g2v_gemm_desc* d) {
   return rows >= 1024 || (rows >= 256 && d->N >= 4096);
 }
 
-int g2v_gemm_8p_launch(const g2v_gemm_desc* d, hipStream_t s) {
-  P8Args a;
-  a.ngroups = 0; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
-  a.tiles_n = d->N / BN; a.flags = d->flags;
-  // 32 resident tiles per XCD: sm x sn supertile of 4 x 8 (or all of N when narrower)
-  a.sn = a.tiles_n < 8 ? a.tiles_n : 8;
-  a.sm = 32 / a.sn > 1 ? 32 / a.sn : 1;
-  int order[2] = {0, 1};
-  if (d->ngroups == 2 && d->g[1].M > d->g[0].M) { order[0] = 1; order[1] = 0; }
-  // tile height from the large group; the small (und) group rides along with the same height
-  const long m_big = d->g[order[0]].M;
-  const long m_small = d->ngroups == 2 ? d->g[order[1]].M : 0;
+// Tile height of the launch (either form): from the large group; the small (und) group rides along with the same height
+int g2v_gemm_8p_height(const g2v_gemm_desc* d) {
+  const int tiles_n = d->N / BN;
+  const int big = d->ngroups == 2 && d->g[1].M > d->g[0].M ? 1 : 0;
+  const long m_big = d->g[big].M;
+  const long m_small = d->ngroups == 2 ? d->g[1 - big].M : 0;
   int bm = 256;
   {
     // cost of a launch = rounds of 256 resident tiles x tile height, with a handicap for shorter tiles (less reuse per
@@ -671,7 +667,7 @@ int g2v_gemm_8p_launch(const g2v_gemm_desc* d, hipStream_t s) {
     for (int k = 0; k < 6; ++k) {
       const int h = hs[k];
       const int small_rows = m_small > 0 ? (int)((m_small + h - 1) / h) : 0;
-      const long tiles = ((m_big + h - 1) / h + small_rows) * a.tiles_n;
+      const long tiles = ((m_big + h - 1) / h + small_rows) * tiles_n;
       const long rounds = (tiles + 255) / 256;
       const double c = (double)rounds * h * hc[k];
       if (c < best) { best = c; bm = h; }
@@ -683,18 +679,34 @@ int g2v_gemm_8p_launch(const g2v_gemm_desc* d, hipStream_t s) {
   if (d->flags & G2V_GEMM_8P_H288) bm = 288;
   if (d->flags & G2V_GEMM_8P_H224) bm = 224;
   if (d->flags & G2V_GEMM_8P_H160) bm = 160;
-  // four-wave form (gemm_4w.hip) or the eight-wave loops of this file (bit-identical A/B partners): the flags force one, otherwise
-  // by shape class (G2V_GEMM_4W_MASK: bit 0 wide N (gate/up), bit 1 long K (down, fc2), bit 2 other fp32-residual Linears (o-proj),
-  // bit 3 plain bf16 outputs (qkv), bit 4 GELU (fc1); default 6 = what the C3 step measures fastest IN SITU on a power-limited chip)
-  if (!(d->flags & (G2V_GEMM_8P_EIGHT_WAVES | G2V_GEMM_8P_TWO_BARRIER | G2V_GEMM_8P_PIPELINED))) {
-    static int mask = -1;
-    if (mask < 0) {
-      const char* e = getenv("G2V_GEMM_4W_MASK");
-      mask = e ? atoi(e) : 6;
-    }
-    const int cls = d->N >= 8192 ? 1 : (d->K >= 4096 ? 2 : (d->epilogue == G2V_EPI_RES_F32 ? 4 : (d->epilogue == G2V_EPI_GELU ? 16 : 8)));
-    if ((d->flags & G2V_GEMM_8P_FOUR_WAVES) || (mask & cls)) return g2v_gemm_4w_launch(d, bm, order, s);
+  return bm;
+}
+
+// four-wave form (gemm_4w.hip) or the eight-wave loops of this file (bit-identical A/B partners): the flags force one, otherwise
+// by shape class (G2V_GEMM_4W_MASK: bit 0 wide N (gate/up), bit 1 long K (down, fc2), bit 2 other fp32-residual Linears (o-proj),
+// bit 3 plain bf16 outputs (qkv), bit 4 GELU (fc1); default 6 = what the C3 step measures fastest IN SITU on a power-limited chip)
+bool g2v_gemm_8p_four_waves(const g2v_gemm_desc* d) {
+  if (d->flags & (G2V_GEMM_8P_EIGHT_WAVES | G2V_GEMM_8P_TWO_BARRIER | G2V_GEMM_8P_PIPELINED)) return false;
+  static int mask = -1;
+  if (mask < 0) {
+    const char* e = getenv("G2V_GEMM_4W_MASK");
+    mask = e ? atoi(e) : 6;
   }
+  const int cls = d->N >= 8192 ? 1 : (d->K >= 4096 ? 2 : (d->epilogue == G2V_EPI_RES_F32 ? 4 : (d->epilogue == G2V_EPI_GELU ? 16 : 8)));
+  return (d->flags & G2V_GEMM_8P_FOUR_WAVES) || (mask & cls);
+}
+
+int g2v_gemm_8p_launch(const g2v_gemm_desc* d, hipStream_t s) {
+  P8Args a;
+  a.ngroups = 0; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
+  a.tiles_n = d->N / BN; a.flags = d->flags;
+  // 32 resident tiles per XCD: sm x sn supertile of 4 x 8 (or all of N when narrower)
+  a.sn = a.tiles_n < 8 ? a.tiles_n : 8;
+  a.sm = 32 / a.sn > 1 ? 32 / a.sn : 1;
+  int order[2] = {0, 1};
+  if (d->ngroups == 2 && d->g[1].M > d->g[0].M) { order[0] = 1; order[1] = 0; }
+  const int bm = g2v_gemm_8p_height(d);
+  if (g2v_gemm_8p_four_waves(d)) return g2v_gemm_4w_launch(d, bm, order, s);
   int total = 0;
   for (int i = 0; i < d->ngroups; ++i) {
     const g2v_gemm_group& sg = d->g[order[i]];

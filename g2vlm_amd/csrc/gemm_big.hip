@@ -274,12 +274,9 @@ bool g2v_gemm_big_eligible(const g2v_gemm_desc* d) {
   return rows >= 256 && ((d->K >= 4096 && d->N <= 2048) || (d->K >= 1536 && d->N <= 2048));
 }
 
-int g2v_gemm_big_launch(const g2v_gemm_desc* d, hipStream_t s) {
-  BigArgs a;
-  a.ngroups = 0; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
-  a.tiles_n = d->N / BN; a.flags = d->flags;
-  a.sn = a.tiles_n < 8 ? a.tiles_n : 8;
-  a.sm = (d->flags & G2V_GEMM_SUPERTILE) ? (32 / a.sn > 1 ? 32 / a.sn : 1) : 1;
+// Tile height of the launch (both groups)
+int g2v_gemm_big_height(const g2v_gemm_desc* d) {
+  const int tiles_n = d->N / BN;
   // order groups large-first so the big group's tiles start every XCD range
   int order[2] = {0, 1};
   if (d->ngroups == 2 && d->g[1].M > d->g[0].M) { order[0] = 1; order[1] = 0; }
@@ -287,11 +284,11 @@ int g2v_gemm_big_launch(const g2v_gemm_desc* d, hipStream_t s) {
   for (int i = 0; i < d->ngroups; ++i) Ms[i] = d->g[order[i]].M;
   // the small group uses the same tile height; with M1 << bm it costs ceil(M1/bm) (usually 1) row of tiles
   int tiles1 = 0;
-  if (d->ngroups == 2 && Ms[1] > 0) tiles1 = ((Ms[1] + BM_MAX - 1) / BM_MAX) * a.tiles_n;
+  if (d->ngroups == 2 && Ms[1] > 0) tiles1 = ((Ms[1] + BM_MAX - 1) / BM_MAX) * tiles_n;
   // big group: pick (rounds R, bm) minimising R * effective tile height, tiles <= R * 256 CUs
   int best_bm = BM_MAX; long best_cost = -1;
   for (int R = 1; R <= 256; ++R) {
-    long budget = ((long)R * 256 - tiles1) / a.tiles_n;
+    long budget = ((long)R * 256 - tiles1) / tiles_n;
     if (budget < 1) continue;
     int bm = ceil32((int)((Ms[0] + budget - 1) / budget));
     if (bm > BM_MAX) continue;
@@ -299,6 +296,18 @@ int g2v_gemm_big_launch(const g2v_gemm_desc* d, hipStream_t s) {
     if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_bm = bm; }
     if (best_cost >= 0 && (long)R * 32 > best_cost) break;
   }
+  return best_bm;
+}
+
+int g2v_gemm_big_launch(const g2v_gemm_desc* d, hipStream_t s) {
+  BigArgs a;
+  a.ngroups = 0; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
+  a.tiles_n = d->N / BN; a.flags = d->flags;
+  a.sn = a.tiles_n < 8 ? a.tiles_n : 8;
+  a.sm = (d->flags & G2V_GEMM_SUPERTILE) ? (32 / a.sn > 1 ? 32 / a.sn : 1) : 1;
+  int order[2] = {0, 1};
+  if (d->ngroups == 2 && d->g[1].M > d->g[0].M) { order[0] = 1; order[1] = 0; }
+  const int best_bm = g2v_gemm_big_height(d);
   int total = 0;
   for (int i = 0; i < d->ngroups; ++i) {
     const g2v_gemm_group& sg = d->g[order[i]];

@@ -21,6 +21,8 @@
 
 namespace {
 
+constexpr size_t SK_TICK_BYTES = 64 << 10;                 // the workspace's ticket area (its partials follow it)
+
 struct SkArgs {
   const __bf16* A; const __bf16* W; const __bf16* bias; void* C; const void* res; const float* gamma;
   float* ws; int* tickets;
@@ -218,17 +220,13 @@ bool g2v_gemm_skinny_eligible(const g2v_gemm_desc* d) {
   return true;
 }
 
-int g2v_gemm_skinny_launch(const g2v_gemm_desc* d, hipStream_t s) {
-  const g2v_gemm_group* sg = nullptr;
-  for (int i = 0; i < d->ngroups; ++i)
-    if (d->g[i].M > 0) sg = &d->g[i];
-  if (!sg) return G2V_OK;
-  SkArgs a{(const __bf16*)sg->A, (const __bf16*)sg->W, (const __bf16*)sg->bias, sg->C, sg->res, (const float*)sg->gamma,
-           nullptr, nullptr, sg->M, d->N, d->K, d->lda, d->ldc, d->ldres, d->flags, 1, 1};
+// The K split of the launch for the one live group of M rows: S slices inside a workgroup, KS across workgroups (KS > 1
+// only with a caller workspace that holds the partials; the launch then keeps tickets and partials in it).
+void g2v_gemm_skinny_split(const g2v_gemm_desc* d, int M, int* S_out, int* KS_out) {
   // K-slices: T = S (inside a workgroup, <= 4 per column group) x KS (across workgroups).  Enough slices that a wave's
   // slice is one trip of U k-steps, and enough waves (~1024) to cover the chip when N is small; at least 2 k-steps each.
   const int cg = d->epilogue == G2V_EPI_SWIGLU ? 2 : 1;
-  const int mts = sg->M <= 16 ? 1 : (sg->M <= 32 ? 2 : 4);
+  const int mts = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
   const int U = mts == 1 ? 6 : (mts == 2 ? 4 : 2);
   const int groups = d->N / 16, blocks = groups / cg, nks = d->K / 64;
   int T = (nks + U - 1) / U;
@@ -244,23 +242,33 @@ int g2v_gemm_skinny_launch(const g2v_gemm_desc* d, hipStream_t s) {
   int KS = cross ? (T + S - 1) / S : 1;
   // the cross-workgroup stage needs the caller's workspace: tickets (int32 per block, zeroed once) then fp32 partials
   // (the ticket area has a FIXED size: partials of one shape must never land where another shape keeps its tickets)
-  constexpr size_t tick_bytes = 64 << 10;
-  if ((size_t)blocks * 4 > tick_bytes) KS = 1;
+  if ((size_t)blocks * 4 > SK_TICK_BYTES) KS = 1;
   const size_t part_bytes = (size_t)blocks * cg * mts * 256 * 4;
   if (cross) {
-    const size_t avail = d->workspace && d->workspace_bytes > (int64_t)tick_bytes ? (size_t)d->workspace_bytes - tick_bytes : 0;
+    const size_t avail = d->workspace && d->workspace_bytes > (int64_t)SK_TICK_BYTES ? (size_t)d->workspace_bytes - SK_TICK_BYTES : 0;
     const int fit = (int)(avail / part_bytes);
     if (KS > fit) KS = fit;
     if (KS <= 1) {                                         // no (or too small a) workspace: all slices inside the workgroup
       KS = 1;
       S = T < 16 / cg ? T : 16 / cg;
       if (64 * cg * S > 512) S = 512 / (64 * cg);
-    } else {
-      a.tickets = reinterpret_cast<int*>(d->workspace);
-      a.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + tick_bytes);
     }
   }
-  a.S = S; a.KS = KS;
+  *S_out = S; *KS_out = KS;
+}
+
+int g2v_gemm_skinny_launch(const g2v_gemm_desc* d, hipStream_t s) {
+  const g2v_gemm_group* sg = nullptr;
+  for (int i = 0; i < d->ngroups; ++i)
+    if (d->g[i].M > 0) sg = &d->g[i];
+  if (!sg) return G2V_OK;
+  SkArgs a{(const __bf16*)sg->A, (const __bf16*)sg->W, (const __bf16*)sg->bias, sg->C, sg->res, (const float*)sg->gamma,
+           nullptr, nullptr, sg->M, d->N, d->K, d->lda, d->ldc, d->ldres, d->flags, 1, 1};
+  g2v_gemm_skinny_split(d, sg->M, &a.S, &a.KS);
+  if (a.KS > 1) {
+    a.tickets = reinterpret_cast<int*>(d->workspace);
+    a.ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->workspace) + SK_TICK_BYTES);
+  }
   switch (d->epilogue) {
     case G2V_EPI_BF16: return launch_epi<G2V_EPI_BF16>(a, s);
     case G2V_EPI_GELU: return launch_epi<G2V_EPI_GELU>(a, s);

@@ -23,6 +23,7 @@ P8_H192, P8_H128, P8_H256, P8_TWO_BARRIER, P8_H288, P8_H224, P8_H160 = 128, 256,
 P8_PIPELINED = 32768                                        # A/B only: round 1's main loop instead of the staggered two-barrier one
 P8_FOUR_WAVES = 65536       # force gemm_4w.hip (four waves, one per SIMD, 128-column wave tiles); without a flag the launcher picks by shape class
 P8_EIGHT_WAVES = 131072     # force gemm_8p.hip's staggered eight-wave loop (round 2's default)
+P8_NO_ROW_SKIP = 262144     # A/B only: wave rows without a valid row run their MFMAs anyway
 F32, BF16 = 0, 1
 NO_CAUSAL = 2 ** 30
 _DEBUG_GEMM_FLAGS = int(os.environ.get("G2V_GEMM_FLAGS", "0"))     # A/B experiments only (tools/, tests -k ...)
@@ -44,6 +45,7 @@ _SIGS = {
     "g2v_version": ([], C.c_int),
     "g2v_arch": ([], C.c_char_p),
     "g2v_gemm_bf16": ([C.POINTER(GemmDesc), _P], C.c_int),
+    "g2v_gemm_route": ([C.POINTER(GemmDesc), C.POINTER(C.c_int32 * 4)], C.c_int),
     "g2v_gemm_f32": ([_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P], C.c_int),
     "g2v_layernorm": ([_P, _I, _I, _P, _P, _F, _P, _I, _I, _I, _I, _P], C.c_int),
     "g2v_rmsnorm": ([_P, _I, _P, _P, _I, _F, _P, _I, _I, _I, _I, _P], C.c_int),
@@ -202,6 +204,22 @@ def _gemm_workspace(device):
 
 def gemm_bf16(groups, N, K, epilogue, out_ld, lda=None, ldres=0, flags=0, ws=None):
     """groups: list (<=2) of dicts {A, W, bias, C, res, gamma, M}; tensors are bf16 except res/gamma/C per epilogue."""
+    _ck(lib().g2v_gemm_bf16(C.byref(_gemm_desc(groups, N, K, epilogue, out_ld, lda, ldres, flags, ws)), _stream()), "g2v_gemm_bf16")
+
+
+GEMM_FORMS = {1: "128x128", 2: "big", 3: "8p", 4: "4w", 5: "skinny"}
+
+
+def gemm_route(groups, N, K, epilogue, out_ld, lda=None, ldres=0, flags=0, ws=None):
+    """What gemm_bf16 with the same arguments launches, without launching: (form name, tile height, S, KS), S / KS = the
+    skinny kernel's K split inside / across workgroups (1 for the tiled forms)."""
+    out = (C.c_int32 * 4)()
+    _ck(lib().g2v_gemm_route(C.byref(_gemm_desc(groups, N, K, epilogue, out_ld, lda, ldres, flags, ws)), C.byref(out)),
+        "g2v_gemm_route")
+    return GEMM_FORMS[out[0]], out[1], out[2], out[3]
+
+
+def _gemm_desc(groups, N, K, epilogue, out_ld, lda, ldres, flags, ws):
     d = GemmDesc()
     flags |= _DEBUG_GEMM_FLAGS
     d.ngroups, d.N, d.K, d.epilogue, d.flags = len(groups), N, K, epilogue, flags
@@ -217,7 +235,7 @@ def gemm_bf16(groups, N, K, epilogue, out_ld, lda=None, ldres=0, flags=0, ws=Non
         gg = d.g[i]
         gg.A, gg.W, gg.bias, gg.C = _p(g["A"]), _p(g["W"]), _p(g.get("bias")), _p(g["C"])
         gg.res, gg.gamma, gg.M = _p(g.get("res")), _p(g.get("gamma")), int(g["M"])
-    _ck(lib().g2v_gemm_bf16(C.byref(d), _stream()), "g2v_gemm_bf16")
+    return d
 
 
 def linear(x, w, bias=None, epilogue=EPI_BF16, out=None, res=None, gamma=None, flags=0, ws=None):

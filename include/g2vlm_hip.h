@@ -74,6 +74,11 @@ typedef struct {
 } g2v_gemm_desc;       /* host struct */
 
 int g2v_gemm_bf16(const g2v_gemm_desc* desc, void* stream);
+/* What g2v_gemm_bf16 launches for `desc` (host only, no launch; tests and tools): out = {form, tile height, S, KS}.
+ * form 1 = 128x128 (gemm.hip), 2 = big tile (gemm_big.hip), 3 = eight-wave 256x256 (gemm_8p.hip), 4 = four-wave
+ * 256x256 (gemm_4w.hip), 5 = skinny (gemm_skinny.hip, height = its m-tile rows 16 / 32 / 64); S / KS = the skinny
+ * kernel's K split inside / across workgroups (1 elsewhere).  Returns what g2v_gemm_bf16 would for a bad descriptor. */
+int g2v_gemm_route(const g2v_gemm_desc* desc, int32_t out[4]);
 
 /* fp32 islands (autocast disabled): Pi3LinearPts3d.proj, Pi3CameraHead linears
  * (transformer_head.py:75, camera_head.py:26-29).  C = [relu](A x W^T + bias) [+ res]            */
