@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libg2vlm_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_8p.hip", "gemm_4w.hip", "gemm_skinny.hip", "attn.hip", "norm_rope.hip", "misc.hip", "decode.hip",
-           "decode_layer.hip", "decode_batch.hip", "decode_shared.hip"]
+           "decode_layer.hip", "decode_batch.hip", "decode_shared.hip", "decode_fp8.hip"]
 
 
 # per-source flags.  attn.hip: hipcc's SLP vectoriser packs neighbouring f32 adds / multiplies of the softmax into v_pk_*_f32,
@@ -28,7 +28,9 @@ FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize"]}
 # kernels that OWN accumulation registers (asm statements name a-registers literally): their resource usage as hipcc reports it
 # (-Rpass-analysis=kernel-resource-usage) is kept beside the object, for every instantiation of the shipped build;
 # tests/test_build_cpu.py reads it (no scratch, the whole AGPR file allocated)
-RESOURCE_AUDIT = ("gemm_4w.hip", "attn.hip")
+# decode_fp8.hip: the e4m3 GEMVs hold up to 12 rows of weights per lane; every instantiation must stay spill-free
+# (tests/test_fp8_decode_cpu.py)
+RESOURCE_AUDIT = ("gemm_4w.hip", "attn.hip", "decode_fp8.hip")
 
 
 def resources_path(src, objdir=None):

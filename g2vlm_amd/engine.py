@@ -109,6 +109,7 @@ class Engine:
         # in `tap_layers` (1-based; split row order), the DINO tokens and the decoder outputs are cloned into it
         self.taps, self.tap_layers = None, ()
         self._decode_gen = 2         # batch-1 decode kernels: 2 = persistent grids (csrc/decode_layer.hip), 1 = csrc/decode.hip
+        self._decode_weights = "bf16"   # what the decode step's Linears stream: "bf16", or "fp8" (e4m3 codes + row scales)
 
     @property
     def decode_gen(self):
@@ -119,9 +120,53 @@ class Engine:
         """A/B switch of the decode kernels.  A captured step belongs to the generation it was captured with: drop it."""
         if gen not in (1, 2):
             raise ValueError("decode_gen: 1 (csrc/decode.hip) or 2 (csrc/decode_layer.hip, default)")
+        if gen != 2 and self._decode_weights == "fp8":
+            raise ValueError("decode_weights == 'fp8' needs the persistent-grid kernels (decode_gen == 2)")
         if gen != self._decode_gen:
             self._decode_cached.clear()
         self._decode_gen = gen
+
+    @property
+    def decode_weights(self):
+        return self._decode_weights
+
+    @decode_weights.setter
+    def decode_weights(self, mode):
+        """Encoding of the weights every decode step streams: "bf16" (default) or "fp8".
+
+        "fp8": the und expert's qkv / o / gate-up / down Linears and lm_head are read as OCP e4m3 codes with one power-of-two
+        scale per output row (g2vlm_amd/quant.py, csrc/decode_fp8.hip): half the weight bytes per token.  It applies to the
+        batch-1 step, the batched step with B <= 8 slots, continuous batching and shared-prefix decode; prefill, recon and the
+        bf16 decode keep their kernels, weights and bits.  The first switch quantises on the host (a few seconds for the real
+        model) and adds `X.w8` / `X.ws` next to every such `X.w` in the weight store; the bf16 tensors stay, prefill needs them.
+        Needs decode_gen == 2 (ValueError otherwise).  A batched step with MORE than 8 slots keeps its bf16 skinny-GEMM Linears,
+        as it keeps them in "bf16" mode: the setting is silently without effect there.
+        A captured step belongs to the encoding it was captured with: changing the mode drops the captured steps."""
+        if mode not in ("bf16", "fp8"):
+            raise ValueError("decode_weights: 'bf16' (default) or 'fp8'")
+        if mode == "fp8":
+            if self._decode_gen != 2:
+                raise ValueError("decode_weights == 'fp8' needs the persistent-grid kernels (decode_gen == 2)")
+            self._quantize_decode_weights()
+        if mode != self._decode_weights:
+            self._decode_cached.clear()
+        self._decode_weights = mode
+
+    def _fp8_names(self):
+        names = [f"L{i}.und.{n}.w" for i in range(self.dims["llm"]["layers"]) for n in ("qkv", "o", "gu", "down")]
+        return names + ["lm_head"]
+
+    def _quantize_decode_weights(self):
+        """X.w8 (uint8 e4m3 codes) / X.ws (fp32 row scales) for every Linear of the decode step, from the bf16 tensors the
+        store holds - i.e. after the q|k|v concatenation and the gate/up interleave (a row permutation: the two commute)."""
+        from .quant import quantize_rows_e4m3
+        t = self.w.t
+        for name in self._fp8_names():
+            base = name[:-2] if name.endswith(".w") else name
+            if base + ".w8" in t:
+                continue
+            q, s = quantize_rows_e4m3(t[name])
+            t[base + ".w8"], t[base + ".ws"] = q.to(self.dev), s.to(self.dev)
 
     # ------------------------------------------------------------------ small caches
     def plan(self, windows, Hq):
@@ -488,7 +533,18 @@ class Engine:
         xr = x.view(-1)
         hp.gather_rows(w["embed"], st["tok"], x)
         hp.mrope_table_into(st["pos"], w["inv_freq"], st["cos"], st["sin"])
-        if self.decode_gen == 2:
+        if self.decode_gen == 2 and self._decode_weights == "fp8":
+            # the persistent-grid kernels on e4m3 weights (csrc/decode_fp8.hip)
+            for i in range(Lc["layers"]):
+                p = f"L{i}.und."
+                hp.gemv_pg_fp8(xr, w[p + "qkv.w8"], w[p + "qkv.ws"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"].view(-1))
+                hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], cache.k[i], cache.v[i], st["ao"],
+                                  st["len"], cache.capacity, st["attn_cap"], Hq, Hkv, 128 ** -0.5, st["ws2"])
+                hp.gemv_pg_fp8(st["ao"].view(-1), w[p + "o.w8"], w[p + "o.ws"], res=xr)
+                hp.gemv_pg_fp8(xr, w[p + "gu.w8"], w[p + "gu.ws"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
+                hp.gemv_pg_fp8(st["act"], w[p + "down.w8"], w[p + "down.ws"], res=xr)
+            hp.gemv_pg_fp8(xr, w["lm_head.w8"], w["lm_head.ws"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
+        elif self.decode_gen == 2:
             # persistent-grid kernels (csrc/decode_layer.hip): 256 workgroups with an equal share of the bytes per launch
             for i in range(Lc["layers"]):
                 p = f"L{i}.und."
@@ -553,7 +609,7 @@ class Engine:
             if sample is not None:
                 st["rng"] = hip.make_rng(sample[0], sample[1], d)
         else:
-            key = (cap, sample is not None, self._decode_gen)
+            key = (cap, sample is not None, self._decode_gen, self._decode_weights)
             st = self._decode_cached.get(key)
             if st is None:
                 self._decode_cached.clear()                   # one bucket resident (0.35-0.6 GB each)
@@ -622,8 +678,20 @@ class Engine:
         hp.mrope_table_into(st["pos"], w["inv_freq"], st["cos"], st["sin"])
         pgb = B <= 8 and st["attn_pg"]      # the persistent-grid GEMVs with B rows per weight pass (csrc/decode_batch.hip)
         pre = st.get("prefix")              # decode_begin_shared: every slot's cache is this prefix + its own suffix block
+        fp8 = pgb and st["fp8"]             # the same GEMVs on e4m3 weights (csrc/decode_fp8.hip)
         for i in range(Lc["layers"]):
             p = f"L{i}.und."
+            if fp8:
+                hp.gemv_pg_batch_fp8(x, w[p + "qkv.w8"], w[p + "qkv.ws"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"])
+                if pre is not None:
+                    self._shared_attn(st, pre, i)
+                else:
+                    hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
+                                      st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
+                hp.gemv_pg_batch_fp8(st["ao"], w[p + "o.w8"], w[p + "o.ws"], res=x)
+                hp.gemv_pg_batch_fp8(x, w[p + "gu.w8"], w[p + "gu.ws"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
+                hp.gemv_pg_batch_fp8(st["act"], w[p + "down.w8"], w[p + "down.ws"], res=x)
+                continue
             if pgb:
                 hp.gemv_pg_batch(x, w[p + "qkv.w"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"])
                 if pre is not None:
@@ -653,7 +721,9 @@ class Engine:
             hp.rmsnorm(x, w[p + "ln2"], w[p + "ln2"], 0, eps, out=h)
             hp.linear(h, w[p + "gu.w"], None, hp.EPI_SWIGLU, out=st["act"], ws=st["gws"])
             hp.linear(st["act"], w[p + "down.w"], None, hp.EPI_RES_F32, out=x, res=x, ws=st["gws"])
-        if pgb:
+        if fp8:
+            hp.gemv_pg_batch_fp8(x, w["lm_head.w8"], w["lm_head.ws"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
+        elif pgb:
             hp.gemv_pg_batch(x, w["lm_head"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
         else:
             hp.rmsnorm(x, w["norm.und"], w["norm.und"], 0, eps, out=h)
@@ -682,6 +752,7 @@ class Engine:
         # 4.7 us at B = 8, 688 workgroups)
         fused_attn = B * ((cap // 64 + 3) // 4) * Hkv <= 512
         st = dict(B=B, cap=cap, steps=0, graph=None, fused_attn=fused_attn, attn_pg=self.decode_gen == 2,
+                  fp8=self._decode_weights == "fp8",           # a slot state (and its captured step) keeps the encoding it opened with
                   ws2=torch.empty(hip.decode_attn_pg_workspace(Hq, Hkv, B) // 4, dtype=torch.float32, device=d),
                   k=[torch.zeros((B, cap, Hkv, 128), dtype=bf, device=d) for _ in range(NL)],
                   v=[torch.zeros((B, cap, Hkv, 128), dtype=bf, device=d) for _ in range(NL)],

@@ -93,6 +93,8 @@ _SIGS = {
     "g2v_sample_rows_bf16": ([_P, _I, _I, _L, _P, _P, _P, _P], C.c_int),
     "g2v_decode_attn_shared_workspace": ([_I, _I, _I, _I, _I], C.c_int64),
     "g2v_decode_attn_shared": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P], C.c_int),
+    "g2v_gemv_pg_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P], C.c_int),
+    "g2v_gemv_pg_batch_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -668,6 +670,29 @@ def gemv_pg_batch(x, w, norm_w=None, eps=0.0, bias=None, out=None, res=None, act
     assert tgt.is_contiguous() and tgt.shape == (B, N // 2 if act else N)
     _ck(lib().g2v_gemv_pg_batch(_p(x), _p(norm_w), float(eps), _p(w), _p(bias), _p(out), _p(res), B, N, K, int(act), _stream()),
         "g2v_gemv_pg_batch")
+    return tgt
+
+
+def gemv_pg_fp8(x, wq, wscale, norm_w=None, eps=0.0, bias=None, out=None, res=None, act=False):
+    """g2v_gemv_pg_fp8: gemv_pg with the weight as e4m3 codes wq uint8 [N,K] and one power-of-two scale per row wscale f32 [N]
+    (g2vlm_amd.quant.quantize_rows_e4m3); the result is gemv_pg's on dequantize_rows(wq, wscale) up to the fp32 summation order."""
+    N, K = wq.shape
+    assert wq.dtype == torch.uint8 and wq.is_contiguous() and wscale.dtype == torch.float32 and wscale.shape == (N,)
+    _ck(lib().g2v_gemv_pg_fp8(_p(x), _p(norm_w), float(eps), _p(wq), _p(wscale), _p(bias), _p(out), _p(res), N, K, int(act), _stream()),
+        "g2v_gemv_pg_fp8")
+    return res if res is not None else out
+
+
+def gemv_pg_batch_fp8(x, wq, wscale, norm_w=None, eps=0.0, bias=None, out=None, res=None, act=False):
+    """g2v_gemv_pg_batch_fp8: gemv_pg_batch (B <= 8 rows, weights streamed once) with e4m3 weights as gemv_pg_fp8."""
+    N, K = wq.shape
+    B = x.shape[0]
+    assert wq.dtype == torch.uint8 and wq.is_contiguous() and wscale.dtype == torch.float32 and wscale.shape == (N,)
+    assert x.dim() == 2 and x.shape[1] == K and x.is_contiguous() and (x.dtype == torch.float32) == (norm_w is not None)
+    tgt = res if res is not None else out
+    assert tgt.is_contiguous() and tgt.shape == (B, N // 2 if act else N)
+    _ck(lib().g2v_gemv_pg_batch_fp8(_p(x), _p(norm_w), float(eps), _p(wq), _p(wscale), _p(bias), _p(out), _p(res), B, N, K, int(act),
+                                    _stream()), "g2v_gemv_pg_batch_fp8")
     return tgt
 
 

@@ -86,6 +86,7 @@ class G2VLM:
         self.hidden_size = self.dims["llm"]["hidden"]
         self.use_moe = "Mo" in getattr(config.llm_config, "layer_module", "Qwen2VLMoTDecoderLayer")
         self.use_decode_graph = True         # capture the per-token step in a hipGraph (generate_text)
+        self._decode_weights = "bf16"        # what every decode step streams its Linear weights as: "bf16" or "fp8" (Engine.decode_weights)
         self.sample_seed = 0                 # Philox key of the next do_sample call (incremented per call)
         self.batch_vit_prefill = True        # chat prefill: consecutive equal-grid images as one ViT + und pass (forward_cache_update_vit_multi)
         self._sd = None
@@ -110,8 +111,22 @@ class G2VLM:
             raise KeyError("config.train_conf_pi3 is set but the state dict has no conf_decoder / conf_head tensors "
                            "(reference g2vlm.py:209-219 builds them for such checkpoints)")
         self.engine = Engine(self.weights, self.dims)
+        self.engine.decode_weights = self._decode_weights
         self._sd = None
         return self
+
+    @property
+    def decode_weights(self):
+        """"bf16" (default) or "fp8": weight-only e4m3 decode (Engine.decode_weights).  Prefill and recon are not affected."""
+        return self._decode_weights
+
+    @decode_weights.setter
+    def decode_weights(self, mode):
+        if mode not in ("bf16", "fp8"):
+            raise ValueError("decode_weights: 'bf16' (default) or 'fp8'")
+        if self.engine is not None:
+            self.engine.decode_weights = mode
+        self._decode_weights = mode
 
     def cuda(self):
         return self.to("cuda")

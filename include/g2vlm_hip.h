@@ -298,6 +298,16 @@ int g2v_gemv_pg(const void* x, const void* norm_w, float eps, const void* W, con
 int g2v_gemv_pg_batch(const void* x, const void* norm_w, float eps, const void* W, const void* bias,
                       void* out, void* res, int B, int N, int K, int act, void* stream);
 
+/* ---- FP8 weight-only decode (csrc/decode_fp8.hip): the two entry points above with the weight matrix stored as OCP e4m3fn
+ * codes and one power-of-two scale per output row, W[n][k] = e4m3(Wq[n][k]) * wscale[n] (g2vlm_amd/quant.py).  Wq uint8
+ * [N, K], wscale f32 [N]; every other argument, fused form, rounding point and argument error as g2v_gemv_pg /
+ * g2v_gemv_pg_batch.  The scale is applied exactly, so the result is that of the bf16 entry point on the dequantised
+ * matrix up to the order of the fp32 partial sums.  K % 16 == 0; K <= 9216 / 12288 (<= 1536 with norm_w).               */
+int g2v_gemv_pg_fp8(const void* x, const void* norm_w, float eps, const void* Wq, const void* wscale, const void* bias,
+                    void* out, void* res, int N, int K, int act, void* stream);
+int g2v_gemv_pg_batch_fp8(const void* x, const void* norm_w, float eps, const void* Wq, const void* wscale, const void* bias,
+                          void* out, void* res, int B, int N, int K, int act, void* stream);
+
 /* g2v_decode_attn_fused on a persistent grid (same arguments): 256 / Hkv blocks per kv head and scene, each an equal share
  * of the max_len cache rows (the share is fixed by the capacity so that no address depends on the device-side length), one
  * partial per (head, block).  Rows in [Lk_dev[b], max_len) may hold anything.  Hkv <= 128.

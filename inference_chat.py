@@ -11,6 +11,8 @@ parser = argparse.ArgumentParser()
 parser.add_argument("--model-path", type=str, default="InternRobotics/G2VLM-2B-MoT")
 parser.add_argument("--image-path", type=str, default="examples/25_0.jpg")
 parser.add_argument("--question", type=str, default="")
+parser.add_argument("--decode-weights", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: the decode step streams its Linear weights as e4m3 with one power-of-two scale per row")
 
 
 def main(argv=None):

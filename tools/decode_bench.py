@@ -1,9 +1,10 @@
 """Batch-1 decode step in isolation: random und-expert weights at G2VLM-2B-MoT widths, a KV cache of --kv rows, the captured
 step replayed --steps times.  Prints ms per token / tokens per second / achieved HBM GB/s for each requested variant:
 
-    python tools/decode_bench.py --variants gen1,gen2 [--kv 10976] [--steps 300] [--layers 28]
+    python tools/decode_bench.py --variants gen1,gen2,gen2fp8 [--kv 10976] [--steps 300] [--layers 28]
 
-(variant = decode kernel generation).  Under
+(variant = decode kernel generation; gen2fp8 = generation 2 with Engine.decode_weights = "fp8", whose bytes per token count
+1-byte weights plus 4 bytes of scale per row).  The variants alternate round by round in one process.  Under
 `rocprofv3 --kernel-trace --stats` the same command gives the per-kernel table of profiles/r02*_decode_kernels.csv.
 """
 import argparse
@@ -75,27 +76,42 @@ def main():
     wbytes = a.layers * 2 * (L["hidden"] * (L["heads"] + 2 * L["kv_heads"]) * 128 + L["hidden"] * L["heads"] * 128 + 3 * L["hidden"] * L["ffn"]) \
         + 2 * L["vocab"] * L["hidden"]
     kvbytes = a.layers * 2 * 2 * L["kv_heads"] * 128 * a.kv
-    out = {"kv_len": a.kv, "layers": a.layers, "bytes_per_token": wbytes + kvbytes}
+    wrows = a.layers * ((L["heads"] + 2 * L["kv_heads"]) * 128 + L["hidden"] + 2 * L["ffn"] + L["hidden"]) + L["vocab"]
+    wbytes8 = wbytes // 2 + 4 * wrows                         # e4m3 codes + one fp32 scale per output row
+    out = {"kv_len": a.kv, "layers": a.layers, "bytes_per_token": wbytes + kvbytes, "bytes_per_token_fp8": wbytes8 + kvbytes}
+
+    def select(gen, fp8):
+        if not fp8:
+            eng.decode_weights = "bf16"
+        eng.decode_gen = gen
+        if fp8:
+            eng.decode_weights = "fp8"
     if a.batch:
         for B in (int(v) for v in a.batch.split(",")):
             rec = {}
-            for name, gen in (("gemm", 1), ("pgb", 2)):
-                eng.decode_gen = gen                      # gen 1: skinny-GEMM Linears + separate norms; gen 2: gemv_pg_batch (B <= 8)
+            names = [("gemm", 1, False), ("pgb", 2, False)] + ([("pgbfp8", 2, True)] if "gen2fp8" in a.variants.split(",") else [])
+            states = {}
+            for name, gen, fp8 in names:
+                select(gen, fp8)                          # gen 1: skinny-GEMM Linears + separate norms; gen 2: gemv_pg_batch (B <= 8)
                 cache.length = a.kv
-                st = eng.decode_begin_batch([cache] * B, [5] * B, [a.kv] * B, a.steps * (a.rounds + 1) + 8, use_graph=True)
-                ts = []
-                for rd in range(a.rounds + 1):
+                states[name] = eng.decode_begin_batch([cache] * B, [5] * B, [a.kv] * B, a.steps * (a.rounds + 1) + 8, use_graph=True)
+            ts = {name: [] for name, _, _ in names}
+            for rd in range(a.rounds + 1):
+                for name, _, _ in names:                  # a captured step keeps its kernels: the variants alternate round by round
+                    st = states[name]
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
                     for _ in range(a.steps):
                         eng.decode_step_batch(st)
                     torch.cuda.synchronize()
                     if rd:
-                        ts.append((time.perf_counter() - t0) / a.steps)
-                best = min(ts)
-                rec[name] = dict(ms_per_step=round(best * 1e3, 4), tokens_per_s=round(B / best, 1),
-                                 hbm_gb_per_s=round((wbytes + B * kvbytes) / best / 1e9, 1))
-                del st
+                        ts[name].append((time.perf_counter() - t0) / a.steps)
+            for name, _, fp8 in names:
+                best = min(ts[name])
+                nbytes = (wbytes8 if fp8 else wbytes) + B * kvbytes
+                rec[name] = dict(ms_per_step=round(best * 1e3, 4), tokens_per_s=round(B / best, 1), hbm_gb_per_s=round(nbytes / best / 1e9, 1),
+                                 all_ms=[round(x * 1e3, 4) for x in ts[name]])
+            del states
             out[f"B{B}"] = rec
         print(json.dumps(out))
         return
@@ -103,7 +119,7 @@ def main():
     states = {}
     for v in variants:
         gen = int(v[3]) if v[:3] == "gen" and v[3:4].isdigit() else 2
-        eng.decode_gen = gen
+        select(gen, v.endswith("fp8"))
         eng._decode_cached.clear()
         cache.length = a.kv
         st = eng.decode_begin(cache, 5, a.kv, a.steps * (a.rounds + 1) + 8, use_graph=True)
@@ -111,8 +127,7 @@ def main():
     res = {v: [] for v in variants}
     for rd in range(a.rounds + 1):
         for v in variants:
-            st, gen = states[v]
-            eng.decode_gen = gen
+            st, gen = states[v]                           # a captured step keeps the kernels and weights it was captured with
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(a.steps):
@@ -123,8 +138,9 @@ def main():
                 res[v].append(dt)
     for v in variants:
         best = min(res[v])
-        out[v] = dict(ms_per_token=round(best * 1e3, 4), tokens_per_s=round(1 / best, 1), hbm_gb_per_s=round((wbytes + kvbytes) / best / 1e9, 1),
-                      frac_of_8TBps=round((wbytes + kvbytes) / best / 8e12, 4), all_ms=[round(x * 1e3, 4) for x in res[v]])
+        nbytes = (wbytes8 if v.endswith("fp8") else wbytes) + kvbytes
+        out[v] = dict(ms_per_token=round(best * 1e3, 4), tokens_per_s=round(1 / best, 1), hbm_gb_per_s=round(nbytes / best / 1e9, 1),
+                      frac_of_8TBps=round(nbytes / best / 8e12, 4), bytes_per_token=nbytes, all_ms=[round(x * 1e3, 4) for x in res[v]])
     print(json.dumps(out))
 
 
