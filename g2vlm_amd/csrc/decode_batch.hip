@@ -15,6 +15,7 @@
 // Results equal the batch-1 kernels' up to the order of the fp32 partial sums (gemv_pgk splits K by wave).
 #include "common.h"
 #include "decode_util.h"
+#include "decode_dispatch.h"
 #include "g2vlm_hip.h"
 
 namespace {
@@ -256,28 +257,14 @@ __global__ __launch_bounds__(512) void gemv_pgk_kernel(const __bf16* x, const __
 }
 
 template <int XMODE, bool ACT, int NB>
-int launch_pgb(int rb, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W, const __bf16* bias, __bf16* out, float* res,
-               int B, int N, int K, int uq, int ur) {
-#define G2V_PGB(RB_)                                                                                                         \
-  hipLaunchKernelGGL((gemv_pgb_kernel<XMODE, ACT, NB, RB_>), dim3(256), dim3(512), 0, s, x, nw, eps, W, bias, out, res, B, N, K, uq, ur)
-  if constexpr (NB == 8) {
-    if (rb <= 1) G2V_PGB(1); else G2V_PGB(2);
-  } else if constexpr (NB == 4) {
-    if (rb <= 1) G2V_PGB(1); else if (rb <= 2) G2V_PGB(2); else G2V_PGB(3);
-  } else {
-    if (rb <= 1) G2V_PGB(1); else if (rb <= 2) G2V_PGB(2); else if (rb <= 3) G2V_PGB(3); else G2V_PGB(5);
-  }
-#undef G2V_PGB
+int launch_pgb(const pg::Plan& p, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W, const __bf16* bias, __bf16* out,
+               float* res, int B, int N, int K) {
+  pg::with_rb<false, NB, ACT, false>(p.rb, [&](auto rb) {
+    hipLaunchKernelGGL((gemv_pgb_kernel<XMODE, ACT, NB, decltype(rb)::value>), dim3(256), dim3(512), 0, s, x, nw, eps, W, bias, out, res, B, N,
+                       K, p.uq, p.ur);
+  });
   G2V_CHECK_LAUNCH();
   return G2V_OK;
-}
-
-template <int NB>
-int dispatch_pgb(bool norm, bool act, int rb, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W, const __bf16* bias,
-                 __bf16* out, float* res, int B, int N, int K, int uq, int ur) {
-  if (norm && act) return launch_pgb<1, true, NB>(rb, s, x, nw, eps, W, bias, out, res, B, N, K, uq, ur);
-  if (norm) return launch_pgb<1, false, NB>(rb, s, x, nw, eps, W, bias, out, res, B, N, K, uq, ur);
-  return launch_pgb<0, false, NB>(rb, s, x, nw, eps, W, bias, out, res, B, N, K, uq, ur);
 }
 
 }  // namespace
@@ -286,33 +273,24 @@ int dispatch_pgb(bool norm, bool act, int rb, hipStream_t s, const void* x, cons
 // and res are row-major with leading dimensions K, N (N / 2 for act) and N).  The grid is 256 blocks of 8 waves whatever N.
 extern "C" int g2v_gemv_pg_batch(const void* x, const void* norm_w, float eps, const void* W, const void* bias, void* out, void* res,
                                  int B, int N, int K, int act, void* stream) {
-  if (!x || !W || (!out && !res) || B <= 0 || B > 8 || N <= 0 || K <= 0 || (K & 7) || K > 12288) return G2V_ERR_ARG;
-  if (act && ((N & 31) || !out || res || !norm_w)) return G2V_ERR_ARG;
-  const int nch = K / 8;
-  if (norm_w && nch > 192) return G2V_ERR_ARG;               // the fused norm stages whole rows: hidden-size K
+  if (!x || !W || (!out && !res) || (act && (!out || res)) || B <= 0) return G2V_ERR_ARG;
+  pg::Plan p;
+  if (const int rc = pg::plan(B, N, K, act != 0, norm_w != nullptr, false, p)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const __bf16 *Wp = (const __bf16*)W, *bp = (const __bf16*)bias;
-  const int nb = B <= 2 ? 2 : (B <= 4 ? 4 : 8);
-  if (nch > 192) {
-    const int per = (N + 255) / 256, CW = (nch + 7) / 8;
-    if (nb == 2) hipLaunchKernelGGL(gemv_pgk_kernel<2>, dim3(256), dim3(512), 0, s, (const __bf16*)x, Wp, bp, (__bf16*)out, (float*)res, B, N, K, per, CW);
-    else if (nb == 4) hipLaunchKernelGGL(gemv_pgk_kernel<4>, dim3(256), dim3(512), 0, s, (const __bf16*)x, Wp, bp, (__bf16*)out, (float*)res, B, N, K, per, CW);
-    else hipLaunchKernelGGL(gemv_pgk_kernel<8>, dim3(256), dim3(512), 0, s, (const __bf16*)x, Wp, bp, (__bf16*)out, (float*)res, B, N, K, per, CW);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  const int U = act ? N / 2 : N, waves = 256 * 8;
-  const int uq = U / waves, ur = U % waves;
-  const int per_wave = uq + (ur ? 1 : 0);
-  const int rb_cap = nb == 8 ? 2 : (nb == 4 ? 3 : 5);
-  int rb = per_wave;
-  if (rb > rb_cap) {                                         // several equal batches rather than a full one and a remainder
-    const int nbat = (per_wave + rb_cap - 1) / rb_cap;
-    rb = (per_wave + nbat - 1) / nbat;
-  }
-  if (nb == 2 && rb == 4) rb = 5;                            // instantiated batch sizes: 1, 2, 3, 5
   const float* nwp = (const float*)norm_w;
-  if (nb == 2) return dispatch_pgb<2>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
-  if (nb == 4) return dispatch_pgb<4>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
-  return dispatch_pgb<8>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
+  const __bf16 *Wp = (const __bf16*)W, *bp = (const __bf16*)bias;
+  __bf16* op = (__bf16*)out;
+  float* rp = (float*)res;
+  if (p.form == 3)
+    return pg::with_nb(p.nb, [&](auto nb) {
+      hipLaunchKernelGGL(gemv_pgk_kernel<decltype(nb)::value>, dim3(256), dim3(p.threads), 0, s, (const __bf16*)x, Wp, bp, op, rp, B, N, K, p.per, p.kch);
+      G2V_CHECK_LAUNCH();
+      return G2V_OK;
+    });
+  return pg::with_nb(p.nb, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    if (norm_w && act) return launch_pgb<1, true, NB>(p, s, x, nwp, eps, Wp, bp, op, rp, B, N, K);
+    if (norm_w) return launch_pgb<1, false, NB>(p, s, x, nwp, eps, Wp, bp, op, rp, B, N, K);
+    return launch_pgb<0, false, NB>(p, s, x, nwp, eps, Wp, bp, op, rp, B, N, K);
+  });
 }

@@ -13,6 +13,7 @@
 // rounding: a power of two commutes with every rounding of the sum, so this IS the sum over the dequantised weights.
 #include "common.h"
 #include "decode_util.h"
+#include "decode_dispatch.h"
 #include "g2vlm_hip.h"
 
 namespace {
@@ -472,49 +473,26 @@ __global__ __launch_bounds__(64 * PGK8_SMAX) void gemv_pgk8_kernel(const __bf16*
   }
 }
 
-// units (row pairs) per batch of gemv_pgb8_kernel: registers (12 per unit, 16 NB of activation, 2 NB per unit of sums)
-constexpr int pgb8_cap(int nb, bool act) { return nb == 8 ? 2 : 4; }
-
 template <int XMODE, bool ACT, int KCH>
-int pg8_launch(int rb, int threads, hipStream_t s, const void* x, const float* nw, float eps, const uint8_t* W, const float* ws,
-               const __bf16* bias, __bf16* out, float* res, int N, int K) {
-  const int U = ACT ? N / 2 : N, waves = 256 * (threads / 64);
-  const int uq = U / waves, ur = U % waves;
-#define G2V_PG8(RB_)                                                                                                     \
-  hipLaunchKernelGGL((gemv_pg8_kernel<XMODE, ACT, KCH, RB_>), dim3(256), dim3(threads), 0, s, x, nw, eps, W, ws, bias, out, res, N, K, uq, ur)
-  if constexpr (KCH > 4) {                                   // long K: 9 loads per lane and row
-    if (rb <= 1) G2V_PG8(1); else G2V_PG8(2);
-  } else if constexpr (ACT) {
-    if (rb <= 1) G2V_PG8(1); else if (rb <= 2) G2V_PG8(2); else if (rb <= 3) G2V_PG8(3); else if (rb <= 4) G2V_PG8(4); else G2V_PG8(6);
-  } else {
-    if (rb <= 1) G2V_PG8(1); else if (rb <= 2) G2V_PG8(2); else if (rb <= 3) G2V_PG8(3); else if (rb <= 4) G2V_PG8(4);
-    else if (rb <= 6) G2V_PG8(6); else if (rb <= 8) G2V_PG8(8); else G2V_PG8(12);
-  }
-#undef G2V_PG8
+int pg8_launch(const pg::Plan& p, hipStream_t s, const void* x, const float* nw, float eps, const uint8_t* W, const float* ws, const __bf16* bias,
+               __bf16* out, float* res, int N, int K) {
+  pg::with_rb<true, 0, ACT, (KCH > 4)>(p.rb, [&](auto rb) {
+    hipLaunchKernelGGL((gemv_pg8_kernel<XMODE, ACT, KCH, decltype(rb)::value>), dim3(256), dim3(p.threads), 0, s, x, nw, eps, W, ws, bias, out,
+                       res, N, K, p.uq, p.ur);
+  });
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
 
 template <int XMODE, bool ACT, int NB>
-int pgb8_launch(int rb, hipStream_t s, const void* x, const float* nw, float eps, const uint8_t* W, const float* ws, const __bf16* bias,
-                __bf16* out, float* res, int B, int N, int K, int uq, int ur) {
-#define G2V_PGB8(RB_)                                                                                                        \
-  hipLaunchKernelGGL((gemv_pgb8_kernel<XMODE, ACT, NB, RB_>), dim3(256), dim3(512), 0, s, x, nw, eps, W, ws, bias, out, res, B, N, K, uq, ur)
-  constexpr int CAP = pgb8_cap(NB, ACT);
-  if (rb <= 1) G2V_PGB8(1);
-  else if (rb <= 2 || CAP == 2) G2V_PGB8(2);
-  else if constexpr (CAP >= 4) G2V_PGB8(4);
-#undef G2V_PGB8
+int pgb8_launch(const pg::Plan& p, hipStream_t s, const void* x, const float* nw, float eps, const uint8_t* W, const float* ws,
+                const __bf16* bias, __bf16* out, float* res, int B, int N, int K) {
+  pg::with_rb<true, NB, ACT, false>(p.rb, [&](auto rb) {
+    hipLaunchKernelGGL((gemv_pgb8_kernel<XMODE, ACT, NB, decltype(rb)::value>), dim3(256), dim3(512), 0, s, x, nw, eps, W, ws, bias, out, res, B,
+                       N, K, p.uq, p.ur);
+  });
   G2V_CHECK_LAUNCH();
   return G2V_OK;
-}
-
-template <int NB>
-int pgb8_dispatch(bool norm, bool act, int rb, hipStream_t s, const void* x, const float* nw, float eps, const uint8_t* W, const float* ws,
-                  const __bf16* bias, __bf16* out, float* res, int B, int N, int K, int uq, int ur) {
-  if (norm && act) return pgb8_launch<1, true, NB>(rb, s, x, nw, eps, W, ws, bias, out, res, B, N, K, uq, ur);
-  if (norm) return pgb8_launch<1, false, NB>(rb, s, x, nw, eps, W, ws, bias, out, res, B, N, K, uq, ur);
-  return pgb8_launch<0, false, NB>(rb, s, x, nw, eps, W, ws, bias, out, res, B, N, K, uq, ur);
 }
 
 }  // namespace
@@ -523,74 +501,43 @@ int pgb8_dispatch(bool norm, bool act, int rb, hipStream_t s, const void* x, con
 // Every other argument, every fused form and every argument error as g2v_gemv_pg; K % 16 == 0, K <= 9216.
 extern "C" int g2v_gemv_pg_fp8(const void* x, const void* norm_w, float eps, const void* Wq, const void* wscale, const void* bias, void* out,
                                void* res, int N, int K, int act, void* stream) {
-  if (!x || !Wq || !wscale || (!out && !res) || N <= 0 || K <= 0 || (K & 15) || K > 9216) return G2V_ERR_ARG;
-  if (act && ((N & 31) || !out || res || !norm_w)) return G2V_ERR_ARG;
-  if (norm_w && K > 1536) return G2V_ERR_ARG;                // the fused norm keeps the fp32 row in registers: hidden-size K
-  const bool longk = K > 2048;
-  const int U = act ? N / 2 : N;
-  // waves per block: as g2v_gemv_pg (the count 3..8 that splits the units most evenly; ties to more waves for a streaming
-  // kernel, to fewer for a small one), with the byte count of the e4m3 matrix
-  const int rb_cap = longk ? 2 : (act ? 6 : 12);
-  const bool small = (double)N * K / 256.0 < 48.0 * 1024.0;
-  int best = 4;
-  double best_imb = 1e30;
-  for (int t = 0; t < 6; ++t) {
-    const int nwb = small ? 3 + t : 8 - t;
-    const long nw = 256L * nwb;
-    const double per = (double)U / nw;
-    const double imb = per >= 1.0 ? (double)((U + nw - 1) / nw) / per : 1.0 / per;
-    if (small && (U + nw - 1) / nw > rb_cap && best_imb < 1e29) continue;    // a small kernel is ONE batch per wave
-    if (imb < best_imb - 1e-9) { best_imb = imb; best = nwb; }
-  }
-  const long nw = 256L * best;
-  const int per_wave = (int)((U + nw - 1) / nw);
-  int rb = per_wave;
-  if (rb > rb_cap) {                                         // several equal batches rather than a full one and a remainder
-    const int nb = (per_wave + rb_cap - 1) / rb_cap;
-    rb = (per_wave + nb - 1) / nb;
-  }
+  if (!x || !Wq || !wscale || (!out && !res) || (act && (!out || res))) return G2V_ERR_ARG;
+  pg::Plan p;
+  if (const int rc = pg::plan(0, N, K, act != 0, norm_w != nullptr, true, p)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float *nwp = (const float*)norm_w, *wsp = (const float*)wscale;
   const uint8_t* Wp = (const uint8_t*)Wq;
   const __bf16* bp = (const __bf16*)bias;
-  const int threads = 64 * best;
   if (norm_w) {
-    if (act) return pg8_launch<1, true, 2>(rb, threads, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
-    return pg8_launch<1, false, 2>(rb, threads, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
+    if (act) return pg8_launch<1, true, 2>(p, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
+    return pg8_launch<1, false, 2>(p, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
   }
-  if (!longk) return pg8_launch<0, false, 2>(rb, threads, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
-  return pg8_launch<0, false, 9>(rb, threads, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
+  if (p.kch == 2) return pg8_launch<0, false, 2>(p, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
+  return pg8_launch<0, false, 9>(p, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, N, K);
 }
 
 // g2v_gemv_pg_batch with e4m3 weights (Wq, wscale as g2v_gemv_pg_fp8): B = 1..8 rows, K % 16 == 0, K <= 12288.
 extern "C" int g2v_gemv_pg_batch_fp8(const void* x, const void* norm_w, float eps, const void* Wq, const void* wscale, const void* bias,
                                      void* out, void* res, int B, int N, int K, int act, void* stream) {
-  if (!x || !Wq || !wscale || (!out && !res) || B <= 0 || B > 8 || N <= 0 || K <= 0 || (K & 15) || K > 12288) return G2V_ERR_ARG;
-  if (act && ((N & 31) || !out || res || !norm_w)) return G2V_ERR_ARG;
-  if (norm_w && K > 1536) return G2V_ERR_ARG;                // the fused norm stages whole rows: hidden-size K
+  if (!x || !Wq || !wscale || (!out && !res) || (act && (!out || res)) || B <= 0) return G2V_ERR_ARG;
+  pg::Plan p;
+  if (const int rc = pg::plan(B, N, K, act != 0, norm_w != nullptr, true, p)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const uint8_t* Wp = (const uint8_t*)Wq;
   const float *nwp = (const float*)norm_w, *wsp = (const float*)wscale;
   const __bf16* bp = (const __bf16*)bias;
-  const int nb = B <= 2 ? 2 : (B <= 4 ? 4 : 8);
-  if (K > 1536) {
-    const int per = (N + 255) / 256, S = (K / 16 + 63) / 64;   // 2..12 waves
-    if (nb == 2) hipLaunchKernelGGL(gemv_pgk8_kernel<2>, dim3(256), dim3(64 * S), 0, s, (const __bf16*)x, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, per);
-    else if (nb == 4) hipLaunchKernelGGL(gemv_pgk8_kernel<4>, dim3(256), dim3(64 * S), 0, s, (const __bf16*)x, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, per);
-    else hipLaunchKernelGGL(gemv_pgk8_kernel<8>, dim3(256), dim3(64 * S), 0, s, (const __bf16*)x, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, per);
-    G2V_CHECK_LAUNCH();
-    return G2V_OK;
-  }
-  const int U = (N + 1) / 2, waves = 256 * 8;               // units: pairs of rows (act: the gate and the up row of an output)
-  const int uq = U / waves, ur = U % waves;
-  const int per_wave = uq + (ur ? 1 : 0);
-  const int rb_cap = nb == 8 ? pgb8_cap(8, act != 0) : (nb == 4 ? pgb8_cap(4, act != 0) : pgb8_cap(2, act != 0));
-  int rb = per_wave;
-  if (rb > rb_cap) {                                         // several equal batches rather than a full one and a remainder
-    const int nbat = (per_wave + rb_cap - 1) / rb_cap;
-    rb = (per_wave + nbat - 1) / nbat;
-  }
-  if (nb == 2) return pgb8_dispatch<2>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
-  if (nb == 4) return pgb8_dispatch<4>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
-  return pgb8_dispatch<8>(norm_w != nullptr, act != 0, rb, s, x, nwp, eps, Wp, wsp, bp, (__bf16*)out, (float*)res, B, N, K, uq, ur);
+  __bf16* op = (__bf16*)out;
+  float* rp = (float*)res;
+  if (p.form == 3)                                           // 2..12 waves
+    return pg::with_nb(p.nb, [&](auto nb) {
+      hipLaunchKernelGGL(gemv_pgk8_kernel<decltype(nb)::value>, dim3(256), dim3(p.threads), 0, s, (const __bf16*)x, Wp, wsp, bp, op, rp, B, N, K, p.per);
+      G2V_CHECK_LAUNCH();
+      return G2V_OK;
+    });
+  return pg::with_nb(p.nb, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    if (norm_w && act) return pgb8_launch<1, true, NB>(p, s, x, nwp, eps, Wp, wsp, bp, op, rp, B, N, K);
+    if (norm_w) return pgb8_launch<1, false, NB>(p, s, x, nwp, eps, Wp, wsp, bp, op, rp, B, N, K);
+    return pgb8_launch<0, false, NB>(p, s, x, nwp, eps, Wp, wsp, bp, op, rp, B, N, K);
+  });
 }

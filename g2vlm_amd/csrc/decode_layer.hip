@@ -17,6 +17,7 @@
 #include "common.h"
 #include "decode_util.h"
 #include "decode_attn_pg.h"
+#include "decode_dispatch.h"
 #include "g2vlm_hip.h"
 
 #ifdef G2V_STAMPS
@@ -202,21 +203,12 @@ __global__ __launch_bounds__(256, 2) void decode_attn_pg_kernel(AttnArgs a G2V_S
 }
 
 template <int XMODE, bool ACT, int KCH>
-int gemv_pg_launch_rb(int rb, int blocks, int threads, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W,
-                      const __bf16* bias, __bf16* out, float* res, int N, int K) {
-  const int U = ACT ? N / 2 : N, waves = blocks * (threads / 64);
-  const int uq = U / waves, ur = U % waves;
-#define G2V_PG(RB_)                                                                                                      \
-  hipLaunchKernelGGL((gemv_pg_kernel<XMODE, ACT, KCH, RB_>), dim3(blocks), dim3(threads), 0, s, x, nw, eps, W, bias, out, res, N, K, uq, ur G2V_STAMP_PASS)
-  if constexpr (KCH > 8) {                                   // long K: one row per batch (18 loads per lane; two rows spill)
-    G2V_PG(1);
-  } else if constexpr (ACT) {
-    if (rb <= 1) G2V_PG(1); else if (rb <= 2) G2V_PG(2); else if (rb <= 3) G2V_PG(3); else if (rb <= 4) G2V_PG(4); else G2V_PG(5);
-  } else {
-    if (rb <= 1) G2V_PG(1); else if (rb <= 2) G2V_PG(2); else if (rb <= 3) G2V_PG(3); else if (rb <= 4) G2V_PG(4);
-    else if (rb <= 5) G2V_PG(5); else if (rb <= 6) G2V_PG(6); else G2V_PG(8);
-  }
-#undef G2V_PG
+int gemv_pg_launch(const pg::Plan& p, hipStream_t s, const void* x, const float* nw, float eps, const __bf16* W, const __bf16* bias,
+                   __bf16* out, float* res, int N, int K) {
+  pg::with_rb<false, 0, ACT, (KCH > 8)>(p.rb, [&](auto rb) {
+    hipLaunchKernelGGL((gemv_pg_kernel<XMODE, ACT, KCH, decltype(rb)::value>), dim3(256), dim3(p.threads), 0, s, x, nw, eps, W, bias, out,
+                       res, N, K, p.uq, p.ur G2V_STAMP_PASS);
+  });
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
@@ -228,48 +220,32 @@ int gemv_pg_launch_rb(int rb, int blocks, int threads, hipStream_t s, const void
 //                   else x is bf16[K].
 //   act != 0: W = gate/up interleaved per 16 rows, N = 2F rows; out bf16[F] = bf16(bf16(silu(g)) * u) (modeling_qwen2_vl.py:519-521).
 //   res != NULL: res[n] (f32) += bf16(y[n] + bias[n]); else out[n] = that.
-// K % 8 == 0, K <= 9216.  The grid is 256 blocks whatever N: see the header of this file.
+// K % 8 == 0, K <= 9216.  The grid is 256 blocks whatever N: see the header of this file; block size and batch depth: decode_dispatch.h.
 extern "C" int g2v_gemv_pg(const void* x, const void* norm_w, float eps, const void* W, const void* bias, void* out, void* res, int N,
                            int K, int act, void* stream) {
-  if (!x || !W || (!out && !res) || N <= 0 || K <= 0 || (K & 7) || K > 9216) return G2V_ERR_ARG;
-  if (act && ((N & 31) || !out || res || !norm_w)) return G2V_ERR_ARG;      // the activation form is the MLP's first half: norm fused
-  const int kch = (K / 8 + 63) / 64;
-  if (norm_w && kch > 3) return G2V_ERR_ARG;                 // the fused norm keeps the fp32 row in registers: hidden-size K
-  const int U = act ? N / 2 : N;
-  // waves per block: the count (3..8) that splits the units most evenly over 256 blocks; a wave then takes ceil(U / waves)
-  // units.  Ties go to MORE waves for a streaming kernel (loads in flight per CU) and to FEWER, fatter waves for a small one
-  // (< 48 KB per CU: all of it is in flight either way, and 1536 waves take ~1.4 us to dispatch - half of a 3 us kernel,
-  // profiles/r02f_decode_stamps.txt: wave life 2.1 us, kernel span 3.5 us)
-  const int rb_cap0 = kch > 3 ? 1 : (act ? 5 : 8);
-  const bool small = (double)N * K * 2.0 / 256.0 < 48.0 * 1024.0;
-  int best = 4;
-  double best_imb = 1e30;
-  for (int t = 0; t < 6; ++t) {
-    const int nwb = small ? 3 + t : 8 - t;
-    const long nw = 256L * nwb;
-    const double per = (double)U / nw;
-    const double imb = per >= 1.0 ? (double)((U + nw - 1) / nw) / per : 1.0 / per;
-    if (small && (U + nw - 1) / nw > rb_cap0 && best_imb < 1e29) continue;   // a small kernel is ONE batch per wave
-    if (imb < best_imb - 1e-9) { best_imb = imb; best = nwb; }
-  }
-  const long nw = 256L * best;
-  const int per_wave = (int)((U + nw - 1) / nw);
-  const int rb_cap = rb_cap0;                                // registers: ROWS x KCH x 4 per batch
-  int rb = per_wave;
-  if (rb > rb_cap) {                                         // several equal batches rather than a full one and a remainder
-    const int nb = (per_wave + rb_cap - 1) / rb_cap;
-    rb = (per_wave + nb - 1) / nb;
-  }
+  if (!x || !W || (!out && !res) || (act && (!out || res))) return G2V_ERR_ARG;
+  pg::Plan p;
+  if (const int rc = pg::plan(0, N, K, act != 0, norm_w != nullptr, false, p)) return rc;
   hipStream_t s = (hipStream_t)stream;
   const float* nwp = (const float*)norm_w;
   const __bf16 *Wp = (const __bf16*)W, *bp = (const __bf16*)bias;
-  const int threads = 64 * best;
   if (norm_w) {
-    if (act) return gemv_pg_launch_rb<1, true, 3>(rb, 256, threads, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
-    return gemv_pg_launch_rb<1, false, 3>(rb, 256, threads, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
+    if (act) return gemv_pg_launch<1, true, 3>(p, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
+    return gemv_pg_launch<1, false, 3>(p, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
   }
-  if (kch <= 3) return gemv_pg_launch_rb<0, false, 3>(rb, 256, threads, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
-  return gemv_pg_launch_rb<0, false, 18>(rb, 256, threads, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
+  if (p.kch == 3) return gemv_pg_launch<0, false, 3>(p, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
+  return gemv_pg_launch<0, false, 18>(p, s, x, nwp, eps, Wp, bp, (__bf16*)out, (float*)res, N, K);
+}
+
+// What the four persistent-grid GEMV entry points would launch for a shape, decided by the code they launch with
+// (decode_dispatch.h) and without a device.  B == 0: g2v_gemv_pg / g2v_gemv_pg_fp8; B = 1..8: the batched ones.
+// out = {form (1 gemv_pg*, 2 gemv_pgb*, 3 gemv_pgk*), threads per block, RB (form 3: R), KCH (form 3: CW in bf16, S in e4m3)}.
+extern "C" int g2v_gemv_pg_route(int B, int N, int K, int act, int norm, int fp8, int32_t out[4]) {
+  pg::Plan p;
+  if (!out) return G2V_ERR_ARG;
+  if (const int rc = pg::plan(B, N, K, act != 0, norm != 0, fp8 != 0, p)) return rc;
+  out[0] = p.form; out[1] = p.threads; out[2] = p.rb; out[3] = p.kch;
+  return G2V_OK;
 }
 
 extern "C" int64_t g2v_decode_attn_pg_workspace(int Hq, int Hkv, int batch) {

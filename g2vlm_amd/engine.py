@@ -17,49 +17,7 @@ import os
 import torch
 
 from . import hip
-
-
-class KVCache:
-    """Pre-allocated contiguous replacement of NaiveCache (qwen2vl.py:237-251): same logical content
-    (K post-RoPE, bf16, [len, Hkv, 128] per layer) without the per-call realloc + 4 scatters."""
-
-    def __init__(self, num_layers, n_kv_heads=2, device="cuda", capacity=0):
-        self.num_layers_, self.hkv, self.device = num_layers, n_kv_heads, device
-        self.k = [None] * num_layers
-        self.v = [None] * num_layers
-        self.capacity = 0
-        self.length = 0
-        if capacity:
-            self.reserve(capacity)
-
-    def reserve(self, n):
-        if n <= self.capacity:
-            return
-        cap = max(n, int(self.capacity * 1.5))
-        for i in range(self.num_layers_):
-            nk = torch.empty((cap, self.hkv, 128), dtype=torch.bfloat16, device=self.device)
-            nv = torch.empty_like(nk)
-            if self.k[i] is not None and self.length:
-                nk[:self.length].copy_(self.k[i][:self.length]); nv[:self.length].copy_(self.v[i][:self.length])
-            self.k[i], self.v[i] = nk, nv
-        self.capacity = cap
-
-    # NaiveCache-compatible views
-    @property
-    def num_layers(self):
-        return self.num_layers_
-
-    @property
-    def seq_lens(self):
-        return self.length
-
-    @property
-    def key_cache(self):
-        return {i: (self.k[i][:self.length] if self.length else None) for i in range(self.num_layers_)}
-
-    @property
-    def value_cache(self):
-        return {i: (self.v[i][:self.length] if self.length else None) for i in range(self.num_layers_)}
+from .decode import Decode, KVCache, linear_names, weight_key  # noqa: F401  (KVCache: imported from here by callers)
 
 
 def rope2d_tables(D, seq_len, base=100.0):
@@ -91,7 +49,7 @@ def attn_tile_rows(windows, Hq):
     return 256 if (long_kv or tall) else 128
 
 
-class Engine:
+class Engine(Decode):
     def __init__(self, weights, dims):
         self.w = weights
         self.dims = dims
@@ -153,19 +111,17 @@ class Engine:
         self._decode_weights = mode
 
     def _fp8_names(self):
-        names = [f"L{i}.und.{n}.w" for i in range(self.dims["llm"]["layers"]) for n in ("qkv", "o", "gu", "down")]
-        return names + ["lm_head"]
+        return [weight_key(n) for n in linear_names(self.dims["llm"]["layers"])]
 
     def _quantize_decode_weights(self):
         """X.w8 (uint8 e4m3 codes) / X.ws (fp32 row scales) for every Linear of the decode step, from the bf16 tensors the
         store holds - i.e. after the q|k|v concatenation and the gate/up interleave (a row permutation: the two commute)."""
         from .quant import quantize_rows_e4m3
         t = self.w.t
-        for name in self._fp8_names():
-            base = name[:-2] if name.endswith(".w") else name
+        for base in linear_names(self.dims["llm"]["layers"]):
             if base + ".w8" in t:
                 continue
-            q, s = quantize_rows_e4m3(t[name])
+            q, s = quantize_rows_e4m3(t[weight_key(base)])
             t[base + ".w8"], t[base + ".ws"] = q.to(self.dev), s.to(self.dev)
 
     # ------------------------------------------------------------------ small caches
@@ -520,343 +476,3 @@ class Engine:
         hp.layernorm(x, w["vit.ln_q.w"], w["vit.ln_q.b"], 1e-6, out=h)
         m = hp.linear(h.view(T // 4, 4 * C), w["vit.m0.w"], w["vit.m0.b"], hp.EPI_GELU)
         return hp.linear(m, w["vit.m2.w"], w["vit.m2.b"])
-
-    # ------------------------------------------------------------------ batch-1 decode step
-    def _decode_body(self, cache, st):
-        """One token through 28 und-expert layers + final norm + lm_head + argmax (reference generate_text loop body,
-        g2vlm.py:1088-1125).  Allocation-free and host-state-free: position, cache row and KV length live in `st`
-        on the device and are advanced by the last kernel, so the whole step can be captured in a hipGraph."""
-        w, hp = self.w, hip
-        Lc = self.dims["llm"]
-        H, Hq, Hkv, eps, Fd = Lc["hidden"], Lc["heads"], Lc["kv_heads"], Lc["eps"], Lc["ffn"]
-        x = st["x"]
-        xr = x.view(-1)
-        hp.gather_rows(w["embed"], st["tok"], x)
-        hp.mrope_table_into(st["pos"], w["inv_freq"], st["cos"], st["sin"])
-        if self.decode_gen == 2 and self._decode_weights == "fp8":
-            # the persistent-grid kernels on e4m3 weights (csrc/decode_fp8.hip)
-            for i in range(Lc["layers"]):
-                p = f"L{i}.und."
-                hp.gemv_pg_fp8(xr, w[p + "qkv.w8"], w[p + "qkv.ws"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"].view(-1))
-                hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], cache.k[i], cache.v[i], st["ao"],
-                                  st["len"], cache.capacity, st["attn_cap"], Hq, Hkv, 128 ** -0.5, st["ws2"])
-                hp.gemv_pg_fp8(st["ao"].view(-1), w[p + "o.w8"], w[p + "o.ws"], res=xr)
-                hp.gemv_pg_fp8(xr, w[p + "gu.w8"], w[p + "gu.ws"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
-                hp.gemv_pg_fp8(st["act"], w[p + "down.w8"], w[p + "down.ws"], res=xr)
-            hp.gemv_pg_fp8(xr, w["lm_head.w8"], w["lm_head.ws"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
-        elif self.decode_gen == 2:
-            # persistent-grid kernels (csrc/decode_layer.hip): 256 workgroups with an equal share of the bytes per launch
-            for i in range(Lc["layers"]):
-                p = f"L{i}.und."
-                hp.gemv_pg(xr, w[p + "qkv.w"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"].view(-1))
-                hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], cache.k[i], cache.v[i], st["ao"],
-                                  st["len"], cache.capacity, st["attn_cap"], Hq, Hkv, 128 ** -0.5, st["ws2"])
-                hp.gemv_pg(st["ao"].view(-1), w[p + "o.w"], res=xr)
-                hp.gemv_pg(xr, w[p + "gu.w"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
-                hp.gemv_pg(st["act"], w[p + "down.w"], res=xr)
-            hp.gemv_pg(xr, w["lm_head"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
-        else:
-            for i in range(Lc["layers"]):
-                p = f"L{i}.und."
-                hp.gemv_rmsnorm_bf16(xr, w[p + "ln1"], eps, w[p + "qkv.w"], w[p + "qkv.b"], st["qkv"].view(-1))
-                hp.decode_attn_fused(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], cache.k[i], cache.v[i], st["ao"],
-                                     st["len"], cache.capacity, cache.capacity, Hq, Hkv, 128 ** -0.5, st["ws"])
-                hp.gemv_bf16(st["ao"].view(-1), w[p + "o.w"], None, None, res=xr)
-                hp.gemv_rmsnorm_swiglu_bf16(xr, w[p + "ln2"], eps, w[p + "gu.w"], st["act"])
-                hp.gemv_bf16(st["act"], w[p + "down.w"], None, None, res=xr)
-            hp.gemv_rmsnorm_bf16(xr, w["norm.und"], eps, w["lm_head"], None, st["logits"])
-        if st.get("rng") is not None:                      # do_sample (reference g2vlm.py:1119-1122)
-            hp.sample_rows_bf16(st["logits"], st["tok"], st["amax"], st["rng"])
-        else:
-            hp.argmax_bf16(st["logits"], st["tok"], st["amax"])
-        hp.decode_advance(st["pos"], st["row"], st["len"])
-
-    def _decode_state(self, cache, capacity):
-        """Device-side state of the batch-1 decode step over `cache` (a KVCache whose tensors must not move any more)."""
-        Lc = self.dims["llm"]
-        H, Hq, Hkv, Fd = Lc["hidden"], Lc["heads"], Lc["kv_heads"], Lc["ffn"]
-        d, bf = self.dev, torch.bfloat16
-        i32 = lambda shape: torch.zeros(shape, dtype=torch.int32, device=d)
-        return dict(pos=i32((3, 1)), row=i32((1,)), len=torch.ones((1,), dtype=torch.int32, device=d), tok=i32((1,)),
-                    x=torch.empty((1, H), dtype=torch.float32, device=d), cos=torch.empty((1, 128), dtype=torch.float32, device=d),
-                    sin=torch.empty((1, 128), dtype=torch.float32, device=d), h=torch.empty((1, H), dtype=bf, device=d),
-                    qkv=torch.empty((1, (Hq + 2 * Hkv) * 128), dtype=bf, device=d), q=torch.empty((1, Hq * 128), dtype=bf, device=d),
-                    ao=torch.empty((1, Hq * 128), dtype=bf, device=d), gu=torch.empty(2 * Fd, dtype=bf, device=d),
-                    act=torch.empty(Fd, dtype=bf, device=d), logits=torch.empty(Lc["vocab"], dtype=bf, device=d),
-                    ws=torch.empty(hip.decode_attn_workspace(capacity, Hq) // 4, dtype=torch.float32, device=d),
-                    ws2=torch.empty(hip.decode_attn_pg_workspace(Hq, Hkv, 1) // 4, dtype=torch.float32, device=d),
-                    amax=torch.zeros(129, dtype=torch.int32, device=d), graph=None, cache=cache, user_cache=None, base_len=0, steps=0)
-
-    def decode_begin(self, cache, start_token, pos, max_new_tokens, use_graph=True, sample=None):
-        """Point the device-side decode state at the first step after `cache` (a prefilled KVCache).
-
-        use_graph: the step is replayed from a hipGraph.  Capturing it (a warm-up step, ~200 launches recorded, the graph
-        instantiated) costs ~10 ms, 5 % of a 128-token answer, so the captured step is kept: it runs over an engine-owned
-        KV block sized in 4096-row buckets, the caller's prefill rows are copied into it (630 MB at 11 k rows: 0.3 ms) and
-        `decode_end` copies the appended rows back, which keeps NaiveCache's append semantics (qwen2vl.py:626-634) for the
-        caller's cache.  Eager mode decodes in the caller's cache directly.
-
-        sample = (seed, temperature): the next token is drawn from softmax(logits / temperature) (the reference's
-        do_sample branch, g2vlm.py:1119-1122) instead of argmax; the sampler state lives on the device like the rest."""
-        d = self.dev
-        kv_len = cache.length
-        need = kv_len + max_new_tokens + 1
-        cap = (need + 4095) // 4096 * 4096                    # the attention splits its keys by this bucket: graph and eager alike
-        if not use_graph:
-            cache.reserve(cap)
-            st = self._decode_state(cache, cache.capacity)
-            st["attn_cap"] = cap
-            if sample is not None:
-                st["rng"] = hip.make_rng(sample[0], sample[1], d)
-        else:
-            key = (cap, sample is not None, self._decode_gen, self._decode_weights)
-            st = self._decode_cached.get(key)
-            if st is None:
-                self._decode_cached.clear()                   # one bucket resident (0.35-0.6 GB each)
-                own = KVCache(len(cache.k), self.dims["llm"]["kv_heads"], d, capacity=cap)
-                st = self._decode_state(own, own.capacity)
-                st["attn_cap"] = cap
-                if sample is not None:
-                    st["rng"] = hip.make_rng(sample[0], sample[1], d)
-                s = torch.cuda.Stream(device=d)               # warm up once on a side stream: lazy module loads must not
-                s.wait_stream(torch.cuda.current_stream())    # happen during capture
-                with torch.cuda.stream(s):
-                    self._decode_body(own, st)
-                torch.cuda.current_stream().wait_stream(s)
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g):
-                    self._decode_body(own, st)
-                st["graph"] = g
-                self._decode_cached[key] = st
-            own = st["cache"]
-            for i in range(len(cache.k)):
-                own.k[i][:kv_len].copy_(cache.k[i][:kv_len]); own.v[i][:kv_len].copy_(cache.v[i][:kv_len])
-            own.length = kv_len
-            st["user_cache"] = cache
-        st["pos"].fill_(pos); st["row"].fill_(kv_len); st["len"].fill_(kv_len + 1); st["tok"].fill_(int(start_token))
-        if sample is not None:
-            st["rng"].copy_(hip.make_rng(sample[0], sample[1], d))      # step 0 of this call's stream (the capture warm-up drew once)
-        st["base_len"], st["steps"] = kv_len, 0
-        return st
-
-    def decode_step(self, st):
-        """Run one token.  Returns the device tensor holding the NEXT token id (int32 [1], overwritten every step)."""
-        if st["graph"] is not None:
-            st["graph"].replay()
-        else:
-            self._decode_body(st["cache"], st)
-        st["steps"] += 1
-        st["cache"].length = st["base_len"] + st["steps"]
-        return st["tok"]
-
-    def decode_end(self, st):
-        """Give the caller's cache the rows the decode appended (graph mode decodes in an engine-owned block)."""
-        user = st.get("user_cache")
-        if user is None:
-            return
-        lo, hi = st["base_len"], st["base_len"] + st["steps"]
-        user.reserve(hi)
-        own = st["cache"]
-        for i in range(len(user.k)):
-            user.k[i][lo:hi].copy_(own.k[i][lo:hi]); user.v[i][lo:hi].copy_(own.v[i][lo:hi])
-        user.length = hi
-        st["user_cache"] = None
-
-    # ------------------------------------------------------------------ batched decode (SURVEY 8f-3)
-    def _decode_batch_body(self, st):
-        """One token for each of B scenes (same weights, one KV cache each): the reference loop body (g2vlm.py:1088-1125)
-        with its batch = 1 limit lifted.  Weights are streamed once per step for all scenes: every Linear is an M = B
-        GEMM (skinny MFMA kernel), norms / RoPE / cache write are the row-batched prefill kernels addressing the packed
-        cache [B * cap] by row, attention is the split-KV kernel with one grid slice per scene."""
-        w, hp = self.w, hip
-        Lc = self.dims["llm"]
-        H, Hq, Hkv, eps, Fd = Lc["hidden"], Lc["heads"], Lc["kv_heads"], Lc["eps"], Lc["ffn"]
-        B, cap = st["B"], st["cap"]
-        x, h = st["x"], st["h"]
-        nq, nqkv = Hq * 128, (Hq + 2 * Hkv) * 128
-        hp.gather_rows(w["embed"], st["tok"], x)
-        hp.mrope_table_into(st["pos"], w["inv_freq"], st["cos"], st["sin"])
-        pgb = B <= 8 and st["attn_pg"]      # the persistent-grid GEMVs with B rows per weight pass (csrc/decode_batch.hip)
-        pre = st.get("prefix")              # decode_begin_shared: every slot's cache is this prefix + its own suffix block
-        fp8 = pgb and st["fp8"]             # the same GEMVs on e4m3 weights (csrc/decode_fp8.hip)
-        for i in range(Lc["layers"]):
-            p = f"L{i}.und."
-            if fp8:
-                hp.gemv_pg_batch_fp8(x, w[p + "qkv.w8"], w[p + "qkv.ws"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"])
-                if pre is not None:
-                    self._shared_attn(st, pre, i)
-                else:
-                    hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
-                                      st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
-                hp.gemv_pg_batch_fp8(st["ao"], w[p + "o.w8"], w[p + "o.ws"], res=x)
-                hp.gemv_pg_batch_fp8(x, w[p + "gu.w8"], w[p + "gu.ws"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
-                hp.gemv_pg_batch_fp8(st["act"], w[p + "down.w8"], w[p + "down.ws"], res=x)
-                continue
-            if pgb:
-                hp.gemv_pg_batch(x, w[p + "qkv.w"], norm_w=w[p + "ln1"], eps=eps, bias=w[p + "qkv.b"], out=st["qkv"])
-                if pre is not None:
-                    self._shared_attn(st, pre, i)
-                else:
-                    hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
-                                      st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
-                hp.gemv_pg_batch(st["ao"], w[p + "o.w"], res=x)
-                hp.gemv_pg_batch(x, w[p + "gu.w"], norm_w=w[p + "ln2"], eps=eps, out=st["act"], act=True)
-                hp.gemv_pg_batch(st["act"], w[p + "down.w"], res=x)
-                continue
-            hp.rmsnorm(x, w[p + "ln1"], w[p + "ln1"], 0, eps, out=h)
-            hp.linear(h, w[p + "qkv.w"], w[p + "qkv.b"], hp.EPI_BF16, out=st["qkv"], ws=st["gws"])
-            if pre is not None:
-                self._shared_attn(st, pre, i)
-            elif st["attn_pg"]:
-                hp.decode_attn_pg(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
-                                  st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws2"])
-            elif st["fused_attn"]:
-                hp.decode_attn_fused(st["qkv"], w[p + "qn"], w[p + "kn"], eps, 1, st["cos"], st["sin"], st["k"][i], st["v"][i], st["ao"],
-                                     st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws"])
-            else:
-                hp.qknorm_mrope_cache(st["qkv"], Hq, Hkv, w[p + "qn"], w[p + "qn"], w[p + "kn"], w[p + "kn"], 0, eps, 1, st["cos"],
-                                      st["sin"], st["q"], st["k"][i], st["v"][i], st["row"])
-                hp.decode_attn_batch(st["q"], st["k"][i], st["v"][i], st["ao"], st["len"], cap, cap, Hq, Hkv, 128 ** -0.5, st["ws"])
-            hp.linear(st["ao"], w[p + "o.w"], None, hp.EPI_RES_F32, out=x, res=x, ws=st["gws"])
-            hp.rmsnorm(x, w[p + "ln2"], w[p + "ln2"], 0, eps, out=h)
-            hp.linear(h, w[p + "gu.w"], None, hp.EPI_SWIGLU, out=st["act"], ws=st["gws"])
-            hp.linear(st["act"], w[p + "down.w"], None, hp.EPI_RES_F32, out=x, res=x, ws=st["gws"])
-        if fp8:
-            hp.gemv_pg_batch_fp8(x, w["lm_head.w8"], w["lm_head.ws"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
-        elif pgb:
-            hp.gemv_pg_batch(x, w["lm_head"], norm_w=w["norm.und"], eps=eps, out=st["logits"])
-        else:
-            hp.rmsnorm(x, w["norm.und"], w["norm.und"], 0, eps, out=h)
-            hp.linear(h, w["lm_head"], None, hp.EPI_BF16, out=st["logits"], ws=st["gws"])
-        if st.get("rng") is not None:
-            hp.sample_rows_bf16(st["logits"], st["tok"], st["amax"], st["rng"])
-        else:
-            hp.argmax_rows_bf16(st["logits"], st["tok"], st["amax"])
-        hp.decode_advance_batch(st["pos"], st["row"], st["len"])
-
-    def decode_open_slots(self, n_slots, cap_rows, use_graph=True, sample=None):
-        """Device-side state of a batched decode with `n_slots` scene slots of `cap_rows` cache rows each, all idle
-        (an idle slot attends to one zero key; its row of every GEMM is independent of the others and its ids are
-        ignored).  Scenes enter and leave through decode_set_slot while the captured step keeps replaying: the graph
-        only holds pointers into this state."""
-        Lc = self.dims["llm"]
-        H, Hq, Hkv, Fd, NL = Lc["hidden"], Lc["heads"], Lc["kv_heads"], Lc["ffn"], Lc["layers"]
-        d, bf = self.dev, torch.bfloat16
-        B = int(n_slots)
-        if not (1 <= B <= 64):
-            raise ValueError("batched decode: 1..64 scene slots")
-        cap = (int(cap_rows) + 63) // 64 * 64
-        i32 = lambda vals: torch.tensor(vals, dtype=torch.int32, device=d)
-        # the fused norm + RoPE + append form of the attention kernel holds 206 VGPRs (2 workgroups per CU): one launch less per
-        # layer while the grid fits the chip at once (15.0 vs 12.9 + 4.6 us at B = 1), slower once it does not (34.6 vs 26.9 +
-        # 4.7 us at B = 8, 688 workgroups)
-        fused_attn = B * ((cap // 64 + 3) // 4) * Hkv <= 512
-        st = dict(B=B, cap=cap, steps=0, graph=None, fused_attn=fused_attn, attn_pg=self.decode_gen == 2,
-                  fp8=self._decode_weights == "fp8",           # a slot state (and its captured step) keeps the encoding it opened with
-                  ws2=torch.empty(hip.decode_attn_pg_workspace(Hq, Hkv, B) // 4, dtype=torch.float32, device=d),
-                  k=[torch.zeros((B, cap, Hkv, 128), dtype=bf, device=d) for _ in range(NL)],
-                  v=[torch.zeros((B, cap, Hkv, 128), dtype=bf, device=d) for _ in range(NL)],
-                  pos=i32([[0] * B] * 3), row=i32([j * cap for j in range(B)]), len=i32([1] * B), tok=i32([0] * B),
-                  x=torch.empty((B, H), dtype=torch.float32, device=d), h=torch.empty((B, H), dtype=bf, device=d),
-                  cos=torch.empty((B, 128), dtype=torch.float32, device=d), sin=torch.empty((B, 128), dtype=torch.float32, device=d),
-                  qkv=torch.empty((B, (Hq + 2 * Hkv) * 128), dtype=bf, device=d), q=torch.empty((B, Hq * 128), dtype=bf, device=d),
-                  ao=torch.empty((B, Hq * 128), dtype=bf, device=d), act=torch.empty((B, Fd), dtype=bf, device=d),
-                  logits=torch.empty((B, Lc["vocab"]), dtype=bf, device=d),
-                  ws=torch.empty(B * hip.decode_attn_workspace(cap, Hq) // 4, dtype=torch.float32, device=d),
-                  amax=torch.zeros(129 * B, dtype=torch.int32, device=d),
-                  gws=torch.zeros(hip.GEMM_WS_WORDS, dtype=torch.int32, device=d))
-        if sample is not None:                               # (seed, temperature): draw instead of argmax, every slot its own stream
-            st["rng"] = hip.make_rng(sample[0], sample[1], d)
-        if use_graph:
-            self._capture_batch(st)
-        return st
-
-    def _capture_batch(self, st):
-        """Capture the batched step of `st` into st["graph"] (after one warm-up step whose state changes are undone)."""
-        d = self.dev
-        init = {n: st[n].clone() for n in ("pos", "row", "len", "tok") + (("rng",) if st.get("rng") is not None else ())}
-        s = torch.cuda.Stream(device=d)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self._decode_batch_body(st)                      # lazy module loads must not happen during capture
-        torch.cuda.current_stream().wait_stream(s)
-        for n, t in init.items():
-            st[n].copy_(t)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._decode_batch_body(st)
-        st["graph"] = g
-
-    def decode_set_slot(self, st, j, cache, start_token, position, max_new_tokens):
-        """Put a prefilled scene into slot j: copy its cache rows into the slot's block and point the slot's device-side
-        state at its first decode step.  Runs between replays of the captured step (same stream)."""
-        n, cap = cache.length, st["cap"]
-        if n + max_new_tokens + 1 > cap:
-            raise ValueError(f"scene needs {n + max_new_tokens + 1} cache rows, the slots hold {cap}")
-        for i in range(len(st["k"])):
-            st["k"][i][j, :n].copy_(cache.k[i][:n]); st["v"][i][j, :n].copy_(cache.v[i][:n])
-        st["pos"][:, j] = int(position)
-        st["row"][j] = j * cap + n
-        st["len"][j] = n + 1
-        st["tok"][j] = int(start_token)
-
-    def decode_idle_slot(self, st, j):
-        """Park slot j (its scene left): the captured step keeps advancing every slot, so an idle one is rewound to its
-        first row before it can run past its block."""
-        st["pos"][:, j] = 0
-        st["row"][j] = j * st["cap"]
-        st["len"][j] = 1
-        st["tok"][j] = 0
-
-    def decode_begin_batch(self, caches, start_tokens, positions, max_new_tokens, use_graph=True, sample=None):
-        """Pack B prefilled caches into one [B, cap, Hkv, 128] block per layer and set up the device-side decode state.
-        caches: list of KVCache (one per scene, after their prefills); start_tokens / positions: one int per scene."""
-        B = len(caches)
-        if not (1 <= B <= 64) or len(start_tokens) != B or len(positions) != B:
-            raise ValueError("decode_begin_batch: 1..64 scenes, one start token and one position each")
-        st = self.decode_open_slots(B, max(c.length for c in caches) + max_new_tokens + 1, use_graph, sample)
-        for j, c in enumerate(caches):
-            self.decode_set_slot(st, j, c, start_tokens[j], positions[j], max_new_tokens)
-        return st
-
-    # ------------------------------------------------------------------ shared-prefix decode (several questions, one scene)
-    def _shared_attn(self, st, pre, i):
-        w, Lc = self.w, self.dims["llm"]
-        p = f"L{i}.und."
-        hip.decode_attn_shared(st["qkv"], w[p + "qn"], w[p + "kn"], Lc["eps"], 1, st["cos"], st["sin"], pre.k[i], pre.v[i],
-                               st["prefix_len"], st["k"][i], st["v"][i], st["len"], st["cap"], st["cap"], Lc["heads"], Lc["kv_heads"],
-                               128 ** -0.5, st["ao"], st["ws3"])
-
-    def decode_begin_shared(self, prefix_cache, suffixes, start_tokens, positions, max_new_tokens, use_graph=True, sample=None):
-        """Batched decode of B questions about one scene.  prefix_cache: the KVCache of the shared rows (system prompt,
-        views), read in place and never written; suffixes[j]: a KVCache holding question j's own prefilled rows (the rows
-        that follow the prefix in its single-question cache); start_tokens / positions: one int per question.
-        The state is decode_open_slots' with [B, cap_s, Hkv, 128] suffix blocks (cap_s: the longest question plus
-        max_new_tokens + 1) in place of whole-scene blocks; the attention (g2v_decode_attn_shared) reads the prefix once
-        per step for all questions.  Nothing allocated here depends on the prefix length.  The captured graph holds
-        pointers into prefix_cache: it must not be reallocated while this state decodes."""
-        B = len(suffixes)
-        if not (1 <= B <= 64) or len(start_tokens) != B or len(positions) != B:
-            raise ValueError("decode_begin_shared: 1..64 questions, one start token and one position each")
-        plen = prefix_cache.length
-        if plen < 1:
-            raise ValueError("decode_begin_shared: empty prefix")
-        Lc = self.dims["llm"]
-        st = self.decode_open_slots(B, max(c.length for c in suffixes) + max_new_tokens + 1, use_graph=False, sample=sample)
-        st["prefix"], st["prefix_len"] = prefix_cache, plen
-        st["ws3"] = torch.empty(hip.decode_attn_shared_workspace(Lc["heads"], Lc["kv_heads"], B, plen, st["cap"]) // 4,
-                                dtype=torch.float32, device=self.dev)
-        for j, c in enumerate(suffixes):
-            self.decode_set_slot(st, j, c, start_tokens[j], positions[j], max_new_tokens)
-        if use_graph:
-            self._capture_batch(st)
-        return st
-
-    def decode_step_batch(self, st):
-        """One token per scene.  Returns the device tensor of NEXT token ids (int32 [B], overwritten every step)."""
-        if st["graph"] is not None:
-            st["graph"].replay()
-        else:
-            self._decode_batch_body(st)
-        st["steps"] += 1
-        return st["tok"]

@@ -95,6 +95,7 @@ _SIGS = {
     "g2v_decode_attn_shared": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P, _P], C.c_int),
     "g2v_gemv_pg_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P], C.c_int),
     "g2v_gemv_pg_batch_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
+    "g2v_gemv_pg_route": ([_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32 * 4)], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -671,6 +672,15 @@ def gemv_pg_batch(x, w, norm_w=None, eps=0.0, bias=None, out=None, res=None, act
     _ck(lib().g2v_gemv_pg_batch(_p(x), _p(norm_w), float(eps), _p(w), _p(bias), _p(out), _p(res), B, N, K, int(act), _stream()),
         "g2v_gemv_pg_batch")
     return tgt
+
+
+def gemv_pg_route(B, N, K, act=False, norm=False, fp8=False):
+    """What gemv_pg / gemv_pg_fp8 (B == 0) or gemv_pg_batch / gemv_pg_batch_fp8 (B = 1..8 rows) launch for a [N, K] weight,
+    without a device: (form, threads per block, RB, KCH) with form 1 = gemv_pg*, 2 = gemv_pgb*, 3 = gemv_pgk* kernels (form 3:
+    RB is the kernel's R and KCH its CW in bf16, S in e4m3).  Raises HipError where the entry point refuses the shape."""
+    out = (C.c_int32 * 4)()
+    _ck(lib().g2v_gemv_pg_route(int(B), int(N), int(K), int(act), int(norm), int(fp8), C.byref(out)), "g2v_gemv_pg_route")
+    return tuple(out)
 
 
 def gemv_pg_fp8(x, wq, wscale, norm_w=None, eps=0.0, bias=None, out=None, res=None, act=False):

@@ -308,6 +308,12 @@ int g2v_gemv_pg_fp8(const void* x, const void* norm_w, float eps, const void* Wq
 int g2v_gemv_pg_batch_fp8(const void* x, const void* norm_w, float eps, const void* Wq, const void* wscale, const void* bias,
                           void* out, void* res, int B, int N, int K, int act, void* stream);
 
+/* What the four entry points above launch for a shape, decided by the code they launch with (csrc/decode_dispatch.h);
+ * touches no device.  B == 0: g2v_gemv_pg / g2v_gemv_pg_fp8, B = 1..8: the batched ones; norm: norm_w != NULL.
+ * out = {form: 1 gemv_pg*, 2 gemv_pgb*, 3 gemv_pgk* kernels; threads per block; instantiated RB (form 3: R); KCH (form 3:
+ * CW in bf16, S in e4m3)}.  G2V_ERR_ARG for every shape the entry point refuses.                                        */
+int g2v_gemv_pg_route(int B, int N, int K, int act, int norm, int fp8, int32_t out[4]);
+
 /* g2v_decode_attn_fused on a persistent grid (same arguments): 256 / Hkv blocks per kv head and scene, each an equal share
  * of the max_len cache rows (the share is fixed by the capacity so that no address depends on the device-side length), one
  * partial per (head, block).  Rows in [Lk_dev[b], max_len) may hold anything.  Hkv <= 128.

@@ -456,7 +456,7 @@ for _tag, _m in (("vit_prefill", vit_prefill_rows()), ("text_prefix", TEXT_PREFI
         f"mot_gu_{_tag}": ([0, _m], 17920, 1536, "swiglu", {}),
         f"mot_down_{_tag}": ([0, _m], 1536, 8960, "res_f32_mot", {}),
     })
-for _B in range(1, 9):                             # batched decode (engine._decode_body): no bias on o / down, no gamma
+for _B in range(1, 9):                             # batched decode (decode.Decode._step): no bias on o / down, no gamma
     PRODUCTION[f"decode_qkv_B{_B}"] = ([_B], 2048, 1536, "bf16", {})
     PRODUCTION[f"decode_o_B{_B}"] = ([_B], 1536, 1536, "res_f32", dict(inplace=True, bias=False))
     PRODUCTION[f"decode_gu_B{_B}"] = ([_B], 17920, 1536, "swiglu", {})
