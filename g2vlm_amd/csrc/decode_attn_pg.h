@@ -35,6 +35,16 @@ __device__ __forceinline__ void xch_store(float* base, int off, float v) {
 
 constexpr int KB = 32, GMAX = 8;
 
+// Blocks per (scene, kv head) of g2v_decode_attn_pg and g2v_decode_attn_pg_kv8 = partials per head (2..128: the combine reads
+// <= 128).  256 blocks per scene for one or two scenes; from three scenes on fewer, longer shares (>= 512 blocks in all, >= 8
+// per kv head) - at B = 8 a block with 96 keys spends its life in the prologue (3.0 TB/s), one with 384 keys streams three
+// batches per wave behind it
+inline int decode_attn_pg_nbh(int Hkv, int batch) {
+  const int nbh1 = 256 / Hkv > 128 ? 128 : 256 / Hkv;
+  const int nbhb = 512 / (Hkv * batch) < 8 ? 8 : 512 / (Hkv * batch);
+  return nbhb < nbh1 ? nbhb : nbh1;
+}
+
 struct AttnArgs {
   const __bf16* qkv; const float* qw; const float* kw; const float* cs; const float* sn; float eps; int und_rounding;
   __bf16* kc; __bf16* vc; float* ws; const int* Lk_dev; int Hq, Hkv; float scale; long scene_rows; int cap, S, SW;

@@ -262,12 +262,7 @@ extern "C" int g2v_decode_attn_pg(const void* qkv, const void* q_norm_w, const v
   if (!qkv || !q_norm_w || !k_norm_w || !cos || !sin || !k_cache || !v_cache || !out || !workspace || !Lk_dev || batch <= 0 ||
       batch > 65535 || max_len <= 0 || scene_rows < max_len || Hq <= 0 || Hkv <= 0 || Hkv > 128 || Hq % Hkv || Hq / Hkv > GMAX)
     return G2V_ERR_ARG;
-  // 2..128 partials per head (the combine reads <= 128): 256 blocks per scene for one or two scenes; from three scenes on
-  // fewer, longer shares (>= 512 blocks in all, >= 8 per kv head) - at B = 8 a block with 96 keys spends its life in the
-  // prologue (3.0 TB/s), one with 384 keys streams three batches per wave behind it
-  const int nbh1 = 256 / Hkv > 128 ? 128 : 256 / Hkv;
-  const int nbhb = 512 / (Hkv * batch) < 8 ? 8 : 512 / (Hkv * batch);
-  const int nbh = nbhb < nbh1 ? nbhb : nbh1;
+  const int nbh = decode_attn_pg_nbh(Hkv, batch);
   AttnArgs a{(const __bf16*)qkv, (const float*)q_norm_w, (const float*)k_norm_w, (const float*)cos, (const float*)sin, eps, und_rounding,
              (__bf16*)k_cache, (__bf16*)v_cache, (float*)workspace, (const int*)Lk_dev, Hq, Hkv, scale, (long)scene_rows, max_len, (max_len + nbh - 1) / nbh,
              ((max_len + nbh - 1) / nbh + 3) / 4};

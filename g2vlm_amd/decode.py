@@ -7,12 +7,14 @@ lm_head, argmax or sample, advance.  What differs between the modes is chosen wh
   st["lin"]   one Linear FAMILY, lin(x, name, norm=None, bias=None, out=None, res=None, act=False):
                 gen-1 batch 1 (csrc/decode.hip), gemv_pg (csrc/decode_layer.hip), gemv_pg_batch (csrc/decode_batch.hip), the
                 last two on e4m3 weights (csrc/decode_fp8.hip), or separate RMSNorm + skinny GEMM for more than 8 slots
-  st["attn"]  one attention FORM, attn(layer): decode_attn_pg, decode_attn_fused, qknorm_mrope_cache + decode_attn_batch,
-                or decode_attn_shared (shared-prefix decode)
+  st["attn"]  one attention FORM, attn(layer): decode_attn_pg, decode_attn_pg_kv8 (csrc/decode_kv8.hip: the same over an e4m3
+                cache), decode_attn_fused, qknorm_mrope_cache + decode_attn_batch, or decode_attn_shared (shared-prefix decode)
 
 Selection.  Persistent-grid GEMVs iff decode_gen == 2 and B <= 8, on e4m3 weights iff decode_weights == "fp8" as well.
 Attention: shared if a prefix is set, else the persistent-grid form if decode_gen == 2, else the fused form at batch 1 or
-while its grid fits the chip, else the split form.  A state (and its captured step) keeps what it was built with.
+while its grid fits the chip, else the split form.  The cache of a state without a prefix is e4m3 iff decode_kv == "fp8"
+(which needs decode_gen == 2): st["k"] / st["v"] are then code tensors, st["ks"] / st["vs"] their scales, and the attention is
+decode_attn_pg_kv8 for any slot count.  A state (and its captured step) keeps what it was built with.
 The step is allocation-free and host-state-free: position, cache row and KV length live in the state on the device and are
 advanced by the last kernel, so the whole step can be captured in a hipGraph (`Decode._capture`).
 """
@@ -64,6 +66,36 @@ class KVCache:
         return {i: (self.v[i][:self.length] if self.length else None) for i in range(self.num_layers_)}
 
 
+class KV8Cache:
+    """Engine-owned e4m3 KV blocks of a decode state (Engine.decode_kv == "fp8"): per layer, codes k[i] / v[i] uint8
+    [B, cap, Hkv, 128] and power-of-two scales ks[i] / vs[i] fp32 [B, cap, Hkv] (g2vlm_amd/quant.py's encoding per row and kv
+    head).  The layers are views of one allocation each, so a row of every layer is reached in one indexing operation.
+    Every row starts as zero codes with scale 1."""
+
+    def __init__(self, num_layers, n_slots, capacity, n_kv_heads, device):
+        shape = (num_layers, n_slots, capacity, n_kv_heads)
+        self.kc, self.vc = (torch.zeros(shape + (128,), dtype=torch.uint8, device=device) for _ in range(2))
+        self.ksc, self.vsc = (torch.ones(shape, dtype=torch.float32, device=device) for _ in range(2))
+        self.k, self.v, self.ks, self.vs = (list(t.unbind(0)) for t in (self.kc, self.vc, self.ksc, self.vsc))
+        self.capacity, self.length = capacity, 0
+
+    def put(self, j, cache, n):
+        """Rows [0, n) of the bf16 KVCache `cache`, quantised, into slot j."""
+        for i in range(len(self.k)):
+            hip.kv_quant_e4m3(cache.k[i][:n], self.k[i][j, :n], self.ks[i][j, :n])
+            hip.kv_quant_e4m3(cache.v[i][:n], self.v[i][j, :n], self.vs[i][j, :n])
+
+    def get(self, j, lo, hi, cache):
+        """Rows [lo, hi) of slot j, dequantised (exact), into the same rows of the bf16 KVCache `cache`."""
+        for i in range(len(self.k)):
+            hip.kv_dequant_e4m3(self.k[i][j, lo:hi], self.ks[i][j, lo:hi], out=cache.k[i][lo:hi])
+            hip.kv_dequant_e4m3(self.v[i][j, lo:hi], self.vs[i][j, lo:hi], out=cache.v[i][lo:hi])
+
+    def clear_row0(self, j):
+        self.kc[:, j, 0] = 0; self.vc[:, j, 0] = 0
+        self.ksc[:, j, 0] = 1; self.vsc[:, j, 0] = 1
+
+
 def linear_names(layers):
     """The Linears the decode step streams, as the step names them."""
     return [f"L{i}.und.{n}" for i in range(layers) for n in ("qkv", "o", "gu", "down")] + ["lm_head"]
@@ -109,8 +141,8 @@ def _lin_skinny(w, eps, h, gws):
 
 
 class Decode:
-    """The decode half of Engine (engine.py): needs self.w, self.dims, self.dev, self.decode_gen, self._decode_weights and
-    self._decode_cached."""
+    """The decode half of Engine (engine.py): needs self.w, self.dims, self.dev, self.decode_gen, self._decode_weights,
+    self._decode_kv and self._decode_cached."""
 
     # ------------------------------------------------------------------ the step
     def _step(self, st):
@@ -136,7 +168,8 @@ class Decode:
         (hip.decode_advance if st["flat"] else hip.decode_advance_batch)(st["pos"], st["row"], st["len"])
 
     def _attention(self, st, prefix):
-        """The attention form of `st`: attn(layer) over st["k"] / st["v"] (blocks of scene_rows rows, split by attn_cap)."""
+        """The attention form of `st`: attn(layer) over st["k"] / st["v"] (blocks of scene_rows rows, split by attn_cap; with
+        st["ks"] / st["vs"] when the state's cache is e4m3)."""
         w, Lc = self.w, self.dims["llm"]
         Hq, Hkv, eps, scale = Lc["heads"], Lc["kv_heads"], Lc["eps"], 128 ** -0.5
         d, B, rows, cap = self.dev, st["B"], st["scene_rows"], st["attn_cap"]
@@ -148,6 +181,11 @@ class Decode:
             ws = f32(hip.decode_attn_shared_workspace(Hq, Hkv, B, plen, rows))
             return lambda i: hip.decode_attn_shared(qkv, *norms(i), eps, 1, cos, sin, prefix.k[i], prefix.v[i], plen, k[i], v[i], ln,
                                                     rows, rows, Hq, Hkv, scale, ao, ws)
+        if st["kv"] == "fp8":
+            ks, vs = st["ks"], st["vs"]
+            ws = f32(hip.decode_attn_pg_workspace(Hq, Hkv, B))
+            return lambda i: hip.decode_attn_pg_kv8(qkv, *norms(i), eps, 1, cos, sin, k[i], v[i], ks[i], vs[i], ao, ln, rows, cap, Hq, Hkv,
+                                                    scale, ws)
         if st["gen"] == 2:
             ws = f32(hip.decode_attn_pg_workspace(Hq, Hkv, B))
             return lambda i: hip.decode_attn_pg(qkv, *norms(i), eps, 1, cos, sin, k[i], v[i], ao, ln, rows, cap, Hq, Hkv, scale, ws)
@@ -165,9 +203,10 @@ class Decode:
             hip.decode_attn_batch(q, k[i], v[i], ao, ln, rows, rows, Hq, Hkv, scale, ws)
         return split
 
-    def _decode_state(self, B, k, v, scene_rows, attn_cap, sample=None, flat=False, prefix=None):
+    def _decode_state(self, B, k, v, scene_rows, attn_cap, sample=None, flat=False, prefix=None, scales=None):
         """Device-side state of a decode over the KV blocks k / v (one tensor per layer, scene_rows rows per scene, which must
-        not move any more).  flat: the batch-1 step (1-D activations and logits, batch-1 kernels); else B slots."""
+        not move any more).  flat: the batch-1 step (1-D activations and logits, batch-1 kernels); else B slots.
+        scales = (ks, vs): k / v hold e4m3 codes and these are their scales (KV8Cache)."""
         Lc = self.dims["llm"]
         H, Hq, Hkv, Fd, eps = Lc["hidden"], Lc["heads"], Lc["kv_heads"], Lc["ffn"], Lc["eps"]
         d, bf = self.dev, torch.bfloat16
@@ -176,7 +215,8 @@ class Decode:
         vec = (lambda t: t.view(-1)) if flat else (lambda t: t)
         x, qkv, ao = buf(H, torch.float32), buf((Hq + 2 * Hkv) * 128), buf(Hq * 128)
         st = dict(B=B, cap=scene_rows, scene_rows=scene_rows, attn_cap=attn_cap, steps=0, graph=None, flat=flat, prefix=prefix,
-                  gen=self.decode_gen, k=k, v=v,              # a state keeps the generation and the encoding it was built with
+                  gen=self.decode_gen, k=k, v=v,              # a state keeps the generation and the encodings it was built with
+                  kv="bf16" if scales is None else "fp8", ks=None if scales is None else scales[0], vs=None if scales is None else scales[1],
                   pos=i32([[0] * B] * 3), row=i32([j * scene_rows for j in range(B)]), len=i32([1] * B), tok=i32([0] * B),
                   x=x, qkv=qkv, ao=ao, lin_io=(vec(x), vec(qkv), vec(ao)), act=vec(buf(Fd)), logits=vec(buf(Lc["vocab"])),
                   cos=buf(128, torch.float32), sin=buf(128, torch.float32), amax=torch.zeros(129 * B, dtype=torch.int32, device=d))
@@ -216,29 +256,43 @@ class Decode:
         `decode_end` copies the appended rows back, which keeps NaiveCache's append semantics (qwen2vl.py:626-634) for the
         caller's cache.  Eager mode decodes in the caller's cache directly.
 
+        decode_kv == "fp8": graph and eager alike decode in an engine-owned e4m3 block (KV8Cache) - the caller's rows are
+        quantised into it (one kernel per layer and tensor in place of the copy), `decode_end` returns the appended rows
+        dequantised; eager mode only skips the capture.
+
         sample = (seed, temperature): the next token is drawn from softmax(logits / temperature) (the reference's
         do_sample branch, g2vlm.py:1119-1122) instead of argmax; the sampler state lives on the device like the rest."""
         d = self.dev
         kv_len = cache.length
         need = kv_len + max_new_tokens + 1
         cap = (need + 4095) // 4096 * 4096                    # the attention splits its keys by this bucket: graph and eager alike
-        if not use_graph:
+        kv8 = self._decode_kv == "fp8"
+        if not use_graph and not kv8:
             cache.reserve(cap)
             st = self._decode_state(1, cache.k, cache.v, cache.capacity, cap, sample, flat=True)
             st.update(cache=cache, user_cache=None)
         else:
-            key = (cap, sample is not None, self._decode_gen, self._decode_weights)
+            # an e4m3 state is kept for eager mode too, hence use_graph (always True with a bf16 cache); the weight mode stays last
+            key = (cap, sample is not None, bool(use_graph), self._decode_gen, self._decode_kv, self._decode_weights)
             st = self._decode_cached.get(key)
             if st is None:
                 self._decode_cached.clear()                   # one bucket resident (0.35-0.6 GB each)
-                own = KVCache(len(cache.k), self.dims["llm"]["kv_heads"], d, capacity=cap)
-                st = self._decode_state(1, own.k, own.v, own.capacity, cap, sample, flat=True)
+                if kv8:
+                    own = KV8Cache(len(cache.k), 1, cap, self.dims["llm"]["kv_heads"], d)
+                    st = self._decode_state(1, own.k, own.v, cap, cap, sample, flat=True, scales=(own.ks, own.vs))
+                else:
+                    own = KVCache(len(cache.k), self.dims["llm"]["kv_heads"], d, capacity=cap)
+                    st = self._decode_state(1, own.k, own.v, own.capacity, cap, sample, flat=True)
                 st["cache"] = own
-                self._capture(st)
+                if use_graph:
+                    self._capture(st)
                 self._decode_cached[key] = st
             own = st["cache"]
-            for i in range(len(cache.k)):
-                own.k[i][:kv_len].copy_(cache.k[i][:kv_len]); own.v[i][:kv_len].copy_(cache.v[i][:kv_len])
+            if kv8:
+                own.put(0, cache, kv_len)
+            else:
+                for i in range(len(cache.k)):
+                    own.k[i][:kv_len].copy_(cache.k[i][:kv_len]); own.v[i][:kv_len].copy_(cache.v[i][:kv_len])
             own.length = kv_len
             st["user_cache"] = cache
         st["pos"].fill_(pos); st["row"].fill_(kv_len); st["len"].fill_(kv_len + 1); st["tok"].fill_(int(start_token))
@@ -254,15 +308,19 @@ class Decode:
         return st["tok"]
 
     def decode_end(self, st):
-        """Give the caller's cache the rows the decode appended (graph mode decodes in an engine-owned block)."""
+        """Give the caller's cache the rows the decode appended (graph mode, and either mode with an e4m3 cache, decodes in an
+        engine-owned block; from an e4m3 block the rows come back dequantised: what the decode attended to)."""
         user = st.get("user_cache")
         if user is None:
             return
         lo, hi = st["base_len"], st["base_len"] + st["steps"]
         user.reserve(hi)
         own = st["cache"]
-        for i in range(len(user.k)):
-            user.k[i][lo:hi].copy_(own.k[i][lo:hi]); user.v[i][lo:hi].copy_(own.v[i][lo:hi])
+        if st["kv"] == "fp8":
+            own.get(0, lo, hi, user)
+        else:
+            for i in range(len(user.k)):
+                user.k[i][lo:hi].copy_(own.k[i][lo:hi]); user.v[i][lo:hi].copy_(own.v[i][lo:hi])
         user.length = hi
         st["user_cache"] = None
 
@@ -275,6 +333,11 @@ class Decode:
         if not (1 <= B <= 64):
             raise ValueError("batched decode: 1..64 scene slots")
         cap = (int(cap_rows) + 63) // 64 * 64
+        if self._decode_kv == "fp8" and prefix is None:      # a shared-prefix state keeps bf16 blocks (decode_begin_shared)
+            own = KV8Cache(Lc["layers"], B, cap, Lc["kv_heads"], self.dev)
+            st = self._decode_state(B, own.k, own.v, cap, cap, sample, scales=(own.ks, own.vs))
+            st["cache8"] = own
+            return st
         kv = lambda: [torch.zeros((B, cap, Lc["kv_heads"], 128), dtype=torch.bfloat16, device=self.dev) for _ in range(Lc["layers"])]  # noqa: E731
         return self._decode_state(B, kv(), kv(), cap, cap, sample, prefix=prefix)
 
@@ -294,8 +357,11 @@ class Decode:
         n, cap = cache.length, st["cap"]
         if n + max_new_tokens + 1 > cap:
             raise ValueError(f"scene needs {n + max_new_tokens + 1} cache rows, the slots hold {cap}")
-        for i in range(len(st["k"])):
-            st["k"][i][j, :n].copy_(cache.k[i][:n]); st["v"][i][j, :n].copy_(cache.v[i][:n])
+        if st["kv"] == "fp8":                                # quantised on the way in
+            st["cache8"].put(j, cache, n)
+        else:
+            for i in range(len(st["k"])):
+                st["k"][i][j, :n].copy_(cache.k[i][:n]); st["v"][i][j, :n].copy_(cache.v[i][:n])
         st["pos"][:, j] = int(position)
         st["row"][j] = j * cap + n
         st["len"][j] = n + 1
@@ -303,7 +369,9 @@ class Decode:
 
     def decode_idle_slot(self, st, j):
         """Park slot j (its scene left): the captured step keeps advancing every slot, so an idle one is rewound to its
-        first row before it can run past its block."""
+        first row before it can run past its block.  In an e4m3 cache that row becomes zero codes with scale 1."""
+        if st["kv"] == "fp8":
+            st["cache8"].clear_row0(j)
         st["pos"][:, j] = 0
         st["row"][j] = j * st["cap"]
         st["len"][j] = 1
@@ -328,7 +396,9 @@ class Decode:
         The state is decode_open_slots' with [B, cap_s, Hkv, 128] suffix blocks (cap_s: the longest question plus
         max_new_tokens + 1) in place of whole-scene blocks; the attention (g2v_decode_attn_shared) reads the prefix once
         per step for all questions.  Nothing allocated here depends on the prefix length.  The captured graph holds
-        pointers into prefix_cache: it must not be reallocated while this state decodes."""
+        pointers into prefix_cache: it must not be reallocated while this state decodes.
+        The prefix is the caller's bf16 cache, so these states keep bf16 suffix blocks whatever decode_kv says: the setting
+        is without effect here (an e4m3 prefix would be a second copy of the scene's rows)."""
         B = len(suffixes)
         if not (1 <= B <= 64) or len(start_tokens) != B or len(positions) != B:
             raise ValueError("decode_begin_shared: 1..64 questions, one start token and one position each")

@@ -68,6 +68,7 @@ class Engine(Decode):
         self.taps, self.tap_layers = None, ()
         self._decode_gen = 2         # batch-1 decode kernels: 2 = persistent grids (csrc/decode_layer.hip), 1 = csrc/decode.hip
         self._decode_weights = "bf16"   # what the decode step's Linears stream: "bf16", or "fp8" (e4m3 codes + row scales)
+        self._decode_kv = "bf16"        # what the decode step keeps its KV cache as: "bf16", or "fp8" (e4m3 codes + row scales)
 
     @property
     def decode_gen(self):
@@ -80,6 +81,8 @@ class Engine(Decode):
             raise ValueError("decode_gen: 1 (csrc/decode.hip) or 2 (csrc/decode_layer.hip, default)")
         if gen != 2 and self._decode_weights == "fp8":
             raise ValueError("decode_weights == 'fp8' needs the persistent-grid kernels (decode_gen == 2)")
+        if gen != 2 and self._decode_kv == "fp8":
+            raise ValueError("decode_kv == 'fp8' needs the persistent-grid kernels (decode_gen == 2)")
         if gen != self._decode_gen:
             self._decode_cached.clear()
         self._decode_gen = gen
@@ -109,6 +112,31 @@ class Engine(Decode):
         if mode != self._decode_weights:
             self._decode_cached.clear()
         self._decode_weights = mode
+
+    @property
+    def decode_kv(self):
+        return self._decode_kv
+
+    @decode_kv.setter
+    def decode_kv(self, mode):
+        """Encoding of the KV cache the decode step reads and appends to: "bf16" (default) or "fp8".
+
+        "fp8": every cache row of a kv head is 128 OCP e4m3 codes and one fp32 power-of-two scale (g2vlm_amd/quant.py's
+        encoding per row and head, K and V separately; csrc/decode_kv8.hip): 132 bytes against 256.  code * scale is exactly a
+        bf16 value, so the engine is the bf16 engine whose cache rows have been replaced by dequant(quant(row)), at copy-in
+        and at every append.  It applies to decode_begin (graph and eager: both decode in an engine-owned quantised block, the
+        caller's rows are quantised into it and decode_end returns the appended rows dequantised), to decode_open_slots /
+        decode_set_slot / decode_begin_batch and continuous batching for any slot count.  Prefill, recon and the caller's
+        KVCache stay bf16.  decode_begin_shared keeps bf16 suffix blocks and reads the bf16 prefix in place: the setting is
+        silently without effect there (as decode_weights is for more than 8 slots).
+        Needs decode_gen == 2 (ValueError otherwise).  Changing the mode drops the captured steps."""
+        if mode not in ("bf16", "fp8"):
+            raise ValueError("decode_kv: 'bf16' (default) or 'fp8'")
+        if mode == "fp8" and self._decode_gen != 2:
+            raise ValueError("decode_kv == 'fp8' needs the persistent-grid kernels (decode_gen == 2)")
+        if mode != self._decode_kv:
+            self._decode_cached.clear()
+        self._decode_kv = mode
 
     def _fp8_names(self):
         return [weight_key(n) for n in linear_names(self.dims["llm"]["layers"])]

@@ -42,8 +42,10 @@ def pil_img2rgb(image):
     return image.convert("RGB")
 
 
-def build_model(llm_config, vit_config, dino_config, state_dict, device="cuda", *, decode_weights="bf16"):
-    """decode_weights: "bf16" or "fp8" (weight-only e4m3 decode, G2VLM.decode_weights)."""
+def build_model(llm_config, vit_config, dino_config, state_dict, device="cuda", *, decode_weights="bf16",
+                decode_kv="bf16"):
+    """decode_weights: "bf16" or "fp8" (weight-only e4m3 decode, G2VLM.decode_weights).
+    decode_kv: "bf16" or "fp8" (e4m3 KV cache of the decode step, G2VLM.decode_kv)."""
     llm_config.qk_norm = True
     llm_config.tie_word_embeddings = False
     llm_config.layer_module = "Qwen2VLMoTDecoderLayer"
@@ -57,6 +59,7 @@ def build_model(llm_config, vit_config, dino_config, state_dict, device="cuda", 
                   DINOv3ViTModel(dino_config) if v3 else Dinov2WithRegistersModel(dino_config), config)
     model.load_state_dict(state_dict, strict=False)
     model.decode_weights = decode_weights
+    model.decode_kv = decode_kv
     return model.to(device).eval()
 
 
@@ -98,10 +101,13 @@ class LazySafetensors:
         return self._keys
 
 
-def load_model_and_tokenizer(model_path, device=None, *, decode_weights=None):
-    """decode_weights: None (a Namespace's .decode_weights if it has one, else "bf16"), "bf16" or "fp8"."""
+def load_model_and_tokenizer(model_path, device=None, *, decode_weights=None, decode_kv=None):
+    """decode_weights: None (a Namespace's .decode_weights if it has one, else "bf16"), "bf16" or "fp8"; decode_kv: the same
+    for the decode step's KV cache (.decode_kv)."""
     if decode_weights is None:
         decode_weights = getattr(model_path, "decode_weights", None) or "bf16"
+    if decode_kv is None:
+        decode_kv = getattr(model_path, "decode_kv", None) or "bf16"
     if not isinstance(model_path, (str, os.PathLike)):                      # argparse Namespace (reference bug H6)
         model_path = getattr(model_path, "model_path", None) or getattr(model_path, "model-path", None)
         if model_path is None:
@@ -114,7 +120,7 @@ def load_model_and_tokenizer(model_path, device=None, *, decode_weights=None):
     vit_config = Qwen2VLVisionConfig.from_json_file(os.path.join(model_path, "vit_config.json"))
     dino_config = Dinov2WithRegistersConfig.from_json_file(os.path.join(model_path, "dino_config.json"))
     model = build_model(llm_config, vit_config, dino_config, LazySafetensors(os.path.join(model_path, "model.safetensors")), device,
-                        decode_weights=decode_weights)
+                        decode_weights=decode_weights, decode_kv=decode_kv)
     from transformers import AutoTokenizer
     tokenizer = AutoTokenizer.from_pretrained(model_path, local_files_only=True)
     tokenizer, new_token_ids, _ = add_special_tokens(tokenizer)

@@ -96,6 +96,9 @@ _SIGS = {
     "g2v_gemv_pg_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _P], C.c_int),
     "g2v_gemv_pg_batch_fp8": ([_P, _P, _F, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P], C.c_int),
     "g2v_gemv_pg_route": ([_I, _I, _I, _I, _I, _I, C.POINTER(C.c_int32 * 4)], C.c_int),
+    "g2v_kv_quant_e4m3": ([_P, _L, _I, _P, _P, _P], C.c_int),
+    "g2v_kv_dequant_e4m3": ([_P, _P, _L, _I, _P, _P], C.c_int),
+    "g2v_decode_attn_pg_kv8": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -716,6 +719,43 @@ def decode_attn_pg(qkv, qw, kw, eps, und_rounding, cos, sin, k_cache, v_cache, o
     _ck(lib().g2v_decode_attn_pg(_p(qkv), _p(qw), _p(kw), eps, int(und_rounding), _p(cos), _p(sin), _p(k_cache), _p(v_cache), _p(out),
                                  _p(len_dev), qkv.shape[0], int(scene_rows), int(max_len), Hq, Hkv, scale, _p(workspace), _stream()),
         "g2v_decode_attn_pg")
+    return out
+
+
+def kv_quant_e4m3(src, codes, scales):
+    """g2v_kv_quant_e4m3: src bf16 [rows, Hkv, 128] -> codes uint8 [rows, Hkv, 128] and scales f32 [rows, Hkv], both written in
+    place: g2vlm_amd.quant.quantize_rows_e4m3 on the rows viewed as [rows * Hkv, 128]."""
+    rows, Hkv, D = src.shape
+    assert D == 128 and src.dtype == torch.bfloat16 and codes.dtype == torch.uint8 and scales.dtype == torch.float32
+    assert src.is_contiguous() and codes.is_contiguous() and scales.is_contiguous()
+    assert codes.shape == src.shape and scales.shape == (rows, Hkv)
+    if rows:
+        _ck(lib().g2v_kv_quant_e4m3(_p(src), rows, Hkv, _p(codes), _p(scales), _stream()), "g2v_kv_quant_e4m3")
+    return codes, scales
+
+
+def kv_dequant_e4m3(codes, scales, out=None):
+    """g2v_kv_dequant_e4m3: codes uint8 [rows, Hkv, 128], scales f32 [rows, Hkv] -> bf16 [rows, Hkv, 128] = codes * scales, exact."""
+    rows, Hkv, D = codes.shape
+    if out is None:
+        out = torch.empty(codes.shape, dtype=torch.bfloat16, device=codes.device)
+    assert D == 128 and out.dtype == torch.bfloat16 and codes.dtype == torch.uint8 and scales.dtype == torch.float32
+    assert out.is_contiguous() and codes.is_contiguous() and scales.is_contiguous()
+    assert out.shape == codes.shape and scales.shape == (rows, Hkv)
+    if rows:
+        _ck(lib().g2v_kv_dequant_e4m3(_p(codes), _p(scales), rows, Hkv, _p(out), _stream()), "g2v_kv_dequant_e4m3")
+    return out
+
+
+def decode_attn_pg_kv8(qkv, qw, kw, eps, und_rounding, cos, sin, k_codes, v_codes, k_scale, v_scale, out, len_dev, scene_rows, max_len,
+                       Hq, Hkv, scale, workspace):
+    """g2v_decode_attn_pg_kv8: decode_attn_pg over an e4m3 cache (codes uint8 [B, scene_rows, Hkv, 128], scales f32
+    [B, scene_rows, Hkv]); the new token's K / V rows are appended quantised and attended to as their dequantised values."""
+    assert k_codes.dtype == torch.uint8 and v_codes.dtype == torch.uint8 and k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32
+    _ck(lib().g2v_decode_attn_pg_kv8(_p(qkv), _p(qw), _p(kw), eps, int(und_rounding), _p(cos), _p(sin), _p(k_codes), _p(v_codes),
+                                     _p(k_scale), _p(v_scale), _p(out), _p(len_dev), qkv.shape[0], int(scene_rows), int(max_len), Hq, Hkv,
+                                     scale, _p(workspace), _stream()),
+        "g2v_decode_attn_pg_kv8")
     return out
 
 

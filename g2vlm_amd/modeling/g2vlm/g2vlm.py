@@ -87,6 +87,7 @@ class G2VLM:
         self.use_moe = "Mo" in getattr(config.llm_config, "layer_module", "Qwen2VLMoTDecoderLayer")
         self.use_decode_graph = True         # capture the per-token step in a hipGraph (generate_text)
         self._decode_weights = "bf16"        # what every decode step streams its Linear weights as: "bf16" or "fp8" (Engine.decode_weights)
+        self._decode_kv = "bf16"             # what the decode step keeps its KV cache as: "bf16" or "fp8" (Engine.decode_kv)
         self.sample_seed = 0                 # Philox key of the next do_sample call (incremented per call)
         self.batch_vit_prefill = True        # chat prefill: consecutive equal-grid images as one ViT + und pass (forward_cache_update_vit_multi)
         self._sd = None
@@ -112,6 +113,7 @@ class G2VLM:
                            "(reference g2vlm.py:209-219 builds them for such checkpoints)")
         self.engine = Engine(self.weights, self.dims)
         self.engine.decode_weights = self._decode_weights
+        self.engine.decode_kv = self._decode_kv
         self._sd = None
         return self
 
@@ -127,6 +129,20 @@ class G2VLM:
         if self.engine is not None:
             self.engine.decode_weights = mode
         self._decode_weights = mode
+
+    @property
+    def decode_kv(self):
+        """"bf16" (default) or "fp8": e4m3 KV cache of the decode step (Engine.decode_kv).  Prefill, recon and the caller's
+        KVCache are not affected."""
+        return self._decode_kv
+
+    @decode_kv.setter
+    def decode_kv(self, mode):
+        if mode not in ("bf16", "fp8"):
+            raise ValueError("decode_kv: 'bf16' (default) or 'fp8'")
+        if self.engine is not None:
+            self.engine.decode_kv = mode
+        self._decode_kv = mode
 
     def cuda(self):
         return self.to("cuda")

@@ -338,6 +338,24 @@ int g2v_decode_attn_shared(const void* qkv, const void* q_norm_w, const void* k_
                            const void* cos, const void* sin, const void* k_prefix, const void* v_prefix, int prefix_len,
                            void* k_suffix, void* v_suffix, const void* suffix_len_dev, int batch, int64_t suffix_rows,
                            int suffix_max_len, int Hq, int Hkv, float scale, void* out, void* workspace, void* stream);
+
+/* ---- FP8 KV cache of the decode step (csrc/decode_kv8.hip) ---------------------------------------------------------------
+ * A cache row of one kv head is 128 OCP e4m3fn codes and one fp32 power-of-two scale, 2^ceil(log2(amax / 448)) (a zero row: 1),
+ * K and V separately: the encoding of g2vlm_amd/quant.py applied to the rows viewed as [rows * Hkv, 128].  code * scale is
+ * exactly a bf16 value.
+ * g2v_kv_quant_e4m3:   src bf16 [rows, Hkv, 128] -> codes uint8 [rows, Hkv, 128], scales f32 [rows, Hkv].
+ * g2v_kv_dequant_e4m3: the inverse, exact: out bf16 [rows, Hkv, 128] = codes * scales.
+ * g2v_decode_attn_pg_kv8: g2v_decode_attn_pg with k_cache / v_cache as codes [batch, scene_rows, Hkv, 128] and k_scale /
+ * v_scale f32 [batch, scene_rows, Hkv].  The new token's K row (normalised, rotated, rounded to bf16 as g2v_decode_attn_pg
+ * rounds it) and V row are quantised, written to row Lk_dev[b] - 1 as codes + scale, and attended to as their dequantised
+ * values; the result is g2v_decode_attn_pg's on the dequantised cache up to fp32 summation order.  Rows in
+ * [Lk_dev[b], max_len) may hold any codes and any scales, NaN included.  Same workspace, same argument errors.            */
+int g2v_kv_quant_e4m3(const void* src, int64_t rows, int Hkv, void* codes, void* scales, void* stream);
+int g2v_kv_dequant_e4m3(const void* codes, const void* scales, int64_t rows, int Hkv, void* out, void* stream);
+int g2v_decode_attn_pg_kv8(const void* qkv, const void* q_norm_w, const void* k_norm_w, float eps, int und_rounding,
+                           const void* cos, const void* sin, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
+                           void* out, const void* Lk_dev, int batch, int64_t scene_rows, int max_len, int Hq, int Hkv,
+                           float scale, void* workspace, void* stream);
 #ifdef __cplusplus
 }
 #endif

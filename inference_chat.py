@@ -13,6 +13,8 @@ parser.add_argument("--image-path", type=str, default="examples/25_0.jpg")
 parser.add_argument("--question", type=str, default="")
 parser.add_argument("--decode-weights", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the decode step streams its Linear weights as e4m3 with one power-of-two scale per row")
+parser.add_argument("--decode-kv", choices=("bf16", "fp8"), default="bf16",
+                    help="fp8: the decode step keeps its KV cache as e4m3 with one power-of-two scale per row and kv head")
 
 
 def main(argv=None):

@@ -1,10 +1,12 @@
 """Batch-1 decode step in isolation: random und-expert weights at G2VLM-2B-MoT widths, a KV cache of --kv rows, the captured
 step replayed --steps times.  Prints ms per token / tokens per second / achieved HBM GB/s for each requested variant:
 
-    python tools/decode_bench.py --variants gen1,gen2,gen2fp8 [--kv 10976] [--steps 300] [--layers 28]
+    python tools/decode_bench.py --variants gen1,gen2,gen2fp8,gen2kv8,gen2fp8kv8 [--kv 10976] [--steps 300] [--layers 28]
 
 (variant = decode kernel generation; gen2fp8 = generation 2 with Engine.decode_weights = "fp8", whose bytes per token count
-1-byte weights plus 4 bytes of scale per row).  The variants alternate round by round in one process.  Under
+1-byte weights plus 4 bytes of scale per row; a trailing kv8 = Engine.decode_kv = "fp8", whose bytes count 1-byte cache elements
+plus 4 bytes of scale per row and kv head).  The variants alternate round by round in one process.  With --batch, gen2kv8 /
+gen2fp8kv8 add the batched variants pgbkv8 / pgbfp8kv8, and every variant reports the peak device memory its state added.  Under
 `rocprofv3 --kernel-trace --stats` the same command gives the per-kernel table of profiles/r02*_decode_kernels.csv.
 """
 import argparse
@@ -76,28 +78,41 @@ def main():
     wbytes = a.layers * 2 * (L["hidden"] * (L["heads"] + 2 * L["kv_heads"]) * 128 + L["hidden"] * L["heads"] * 128 + 3 * L["hidden"] * L["ffn"]) \
         + 2 * L["vocab"] * L["hidden"]
     kvbytes = a.layers * 2 * 2 * L["kv_heads"] * 128 * a.kv
+    kvbytes8 = a.layers * 2 * L["kv_heads"] * (128 + 4) * a.kv     # e4m3 codes + one fp32 scale per row and kv head
     wrows = a.layers * ((L["heads"] + 2 * L["kv_heads"]) * 128 + L["hidden"] + 2 * L["ffn"] + L["hidden"]) + L["vocab"]
     wbytes8 = wbytes // 2 + 4 * wrows                         # e4m3 codes + one fp32 scale per output row
-    out = {"kv_len": a.kv, "layers": a.layers, "bytes_per_token": wbytes + kvbytes, "bytes_per_token_fp8": wbytes8 + kvbytes}
+    out = {"kv_len": a.kv, "layers": a.layers, "bytes_per_token": wbytes + kvbytes, "bytes_per_token_fp8": wbytes8 + kvbytes,
+           "bytes_per_token_kv8": wbytes + kvbytes8, "bytes_per_token_fp8_kv8": wbytes8 + kvbytes8}
 
-    def select(gen, fp8):
+    def select(gen, fp8, kv8=False):
         if not fp8:
             eng.decode_weights = "bf16"
+        if not kv8:
+            eng.decode_kv = "bf16"
         eng.decode_gen = gen
         if fp8:
             eng.decode_weights = "fp8"
+        if kv8:
+            eng.decode_kv = "fp8"
     if a.batch:
         for B in (int(v) for v in a.batch.split(",")):
             rec = {}
-            names = [("gemm", 1, False), ("pgb", 2, False)] + ([("pgbfp8", 2, True)] if "gen2fp8" in a.variants.split(",") else [])
-            states = {}
-            for name, gen, fp8 in names:
-                select(gen, fp8)                          # gen 1: skinny-GEMM Linears + separate norms; gen 2: gemv_pg_batch (B <= 8)
+            want = a.variants.split(",")
+            names = [("gemm", 1, False, False), ("pgb", 2, False, False)] + ([("pgbkv8", 2, False, True)] if "gen2kv8" in want else []) \
+                + ([("pgbfp8", 2, True, False)] if "gen2fp8" in want else []) + ([("pgbfp8kv8", 2, True, True)] if "gen2fp8kv8" in want else [])
+            states, peak = {}, {}
+            for name, gen, fp8, kv8 in names:
+                select(gen, fp8, kv8)                     # gen 1: skinny-GEMM Linears + separate norms; gen 2: gemv_pg_batch (B <= 8)
                 cache.length = a.kv
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
                 states[name] = eng.decode_begin_batch([cache] * B, [5] * B, [a.kv] * B, a.steps * (a.rounds + 1) + 8, use_graph=True)
-            ts = {name: [] for name, _, _ in names}
+                torch.cuda.synchronize()
+                peak[name] = torch.cuda.max_memory_allocated() - base
+            ts = {name: [] for name, *_ in names}
             for rd in range(a.rounds + 1):
-                for name, _, _ in names:                  # a captured step keeps its kernels: the variants alternate round by round
+                for name, *_ in names:                    # a captured step keeps its kernels: the variants alternate round by round
                     st = states[name]
                     torch.cuda.synchronize()
                     t0 = time.perf_counter()
@@ -106,11 +121,11 @@ def main():
                     torch.cuda.synchronize()
                     if rd:
                         ts[name].append((time.perf_counter() - t0) / a.steps)
-            for name, _, fp8 in names:
+            for name, _, fp8, kv8 in names:
                 best = min(ts[name])
-                nbytes = (wbytes8 if fp8 else wbytes) + B * kvbytes
+                nbytes = (wbytes8 if fp8 else wbytes) + B * (kvbytes8 if kv8 else kvbytes)
                 rec[name] = dict(ms_per_step=round(best * 1e3, 4), tokens_per_s=round(B / best, 1), hbm_gb_per_s=round(nbytes / best / 1e9, 1),
-                                 all_ms=[round(x * 1e3, 4) for x in ts[name]])
+                                 bytes_per_step=nbytes, state_peak_mb=round(peak[name] / 2 ** 20, 1), all_ms=[round(x * 1e3, 4) for x in ts[name]])
             del states
             out[f"B{B}"] = rec
         print(json.dumps(out))
@@ -119,7 +134,7 @@ def main():
     states = {}
     for v in variants:
         gen = int(v[3]) if v[:3] == "gen" and v[3:4].isdigit() else 2
-        select(gen, v.endswith("fp8"))
+        select(gen, "fp8" in v, v.endswith("kv8"))
         eng._decode_cached.clear()
         cache.length = a.kv
         st = eng.decode_begin(cache, 5, a.kv, a.steps * (a.rounds + 1) + 8, use_graph=True)
@@ -138,7 +153,7 @@ def main():
                 res[v].append(dt)
     for v in variants:
         best = min(res[v])
-        nbytes = (wbytes8 if v.endswith("fp8") else wbytes) + kvbytes
+        nbytes = (wbytes8 if "fp8" in v else wbytes) + (kvbytes8 if v.endswith("kv8") else kvbytes)
         out[v] = dict(ms_per_token=round(best * 1e3, 4), tokens_per_s=round(1 / best, 1), hbm_gb_per_s=round(nbytes / best / 1e9, 1),
                       frac_of_8TBps=round(nbytes / best / 8e12, 4), bytes_per_token=nbytes, all_ms=[round(x * 1e3, 4) for x in res[v]])
     print(json.dumps(out))
