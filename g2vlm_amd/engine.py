@@ -49,7 +49,43 @@ def attn_tile_rows(windows, Hq):
     return 256 if (long_kv or tall) else 128
 
 
+def pack_continuations(start_token, pos, continuations):
+    """Teacher-forced rows of scoring `continuations` (lists of token ids) after a prefill whose next input is `start_token` at
+    mRoPE position `pos`: continuation c = [c0 .. c_{n-1}] becomes the n rows [start, c0 .. c_{n-2}] at positions pos, pos + 1, ..
+    - the tokens and positions generate_text feeds while it produces c - with targets c.  The continuations are packed one
+    after the other.  Returns (input ids, positions, segment lengths, targets), plain lists of L = sum(n) (lengths: one per
+    continuation)."""
+    ids, poss, seg_lens, targets = [], [], [], []
+    for c in continuations:
+        c = [int(t) for t in c]
+        if not c:
+            raise ValueError("an empty continuation has nothing to score")
+        ids += [int(start_token)] + c[:-1]
+        poss += list(range(int(pos), int(pos) + len(c)))
+        seg_lens.append(len(c))
+        targets += c
+    return ids, poss, seg_lens, targets
+
+
+def score_windows(prefix_len, seg_lens):
+    """Attention windows (q0, q_len, k0, k_len, causal) of the packed scoring pass: segment j, query rows [off_j, off_j + n_j)
+    with its K/V at cache rows prefix_len + off_j .., attends to the prefix [0, prefix_len) (every key, non-causal) and
+    causally to its own rows, and to no other segment.  The two windows of a segment share their query rows, so the
+    attention plan merges them in its combine pass (as it merges the local and remote blocks of the view-sharded prefill)."""
+    wins, off = [], 0
+    for n in seg_lens:
+        if prefix_len > 0:
+            wins.append((off, n, 0, prefix_len, False))
+        wins.append((off, n, prefix_len + off, n, True))
+        off += n
+    return tuple(wins)
+
+
 class Engine(Decode):
+    SCORE_MAX_ROWS = 8192        # rows of one score_rows pass: its logits are rows x vocab bf16 (2.5 GB at the real vocabulary)
+    SCORE_MAX_SEGMENTS = 64
+    SCORE_PLANS_KEPT = 32        # attention plans of score_rows kept (one per (prefix_len, seg_lens)); the oldest is dropped beyond
+
     def __init__(self, weights, dims):
         self.w = weights
         self.dims = dims
@@ -69,6 +105,7 @@ class Engine(Decode):
         self._decode_gen = 2         # batch-1 decode kernels: 2 = persistent grids (csrc/decode_layer.hip), 1 = csrc/decode.hip
         self._decode_weights = "bf16"   # what the decode step's Linears stream: "bf16", or "fp8" (e4m3 codes + row scales)
         self._decode_kv = "bf16"        # what the decode step keeps its KV cache as: "bf16", or "fp8" (e4m3 codes + row scales)
+        self._score_plans = {}          # keys of self._tiles that score_rows made, in order of last use
 
     @property
     def decode_gen(self):
@@ -279,6 +316,53 @@ class Engine(Decode):
 
     def embed(self, ids_i32, out):
         return hip.gather_rows(self.w["embed"], ids_i32, out)
+
+    # ------------------------------------------------------------------ scoring: log-probabilities of given continuations
+    def score_rows(self, cache, prefix_len, ids, pos, seg_lens, targets):
+        """Log-probabilities of C given continuations of one prefilled scene, all in ONE teacher-forced pass.
+
+        cache: the scene's KVCache, cache.length == prefix_len.  ids int32 [L], pos int32 [3, L], targets int32 [L] on the
+        device and seg_lens (host ints, sum L) as pack_continuations lays them out.  The L rows are embedded and go through one
+        llm_forward on the und expert (their K/V rows land in cache rows [prefix_len, prefix_len + L), beyond the cache's
+        length) under score_windows' attention; the bf16 final norm feeds ONE lm_head GEMM over all L rows (the skinny kernel up
+        to 64 rows, the tiled ones above) and ONE g2v_logprob_rows_bf16 launch.  Returns (log-probability fp32 [L], rank int32
+        [L]) on the device; nothing here waits for the device once the attention plan of this (prefix_len, seg_lens) exists.
+        On return cache.length is prefix_len again and rows [0, prefix_len) keep their bits (a cache too small for prefix_len
+        + L rows is reallocated and copied, as by any prefill, and stays grown: at most SCORE_MAX_ROWS rows per scene cache).
+        This is a prefill: it reads the bf16 weights and the bf16 cache with the prefill kernels whatever decode_weights and
+        decode_kv are set to."""
+        Lc = self.dims["llm"]
+        L = int(sum(seg_lens))
+        if not 1 <= len(seg_lens) <= self.SCORE_MAX_SEGMENTS or min(seg_lens) < 1:
+            raise ValueError(f"score_rows: 1..{self.SCORE_MAX_SEGMENTS} continuations of at least one token each")
+        if L > self.SCORE_MAX_ROWS:
+            raise ValueError(f"score_rows: {L} rows in one pass, at most {self.SCORE_MAX_ROWS}")
+        assert cache.length == prefix_len and ids.numel() == L and targets.numel() == L and tuple(pos.shape) == (3, L)
+        wins = score_windows(prefix_len, seg_lens)
+        # the plan is built (and uploaded) before the first launch.  An evaluation sweep brings a new (prefix_len, seg_lens) with
+        # nearly every item, so only the SCORE_PLANS_KEPT most recently used ones stay (their device tables are freed in stream
+        # order, behind the launches that read them).  The plan cache is keyed by (windows, heads) alone, so evicting also drops
+        # the plan of another caller that happens to use the identical windows; that caller rebuilds it on its next call -
+        # a little host work, never a wrong result
+        key = (wins, Lc["heads"])
+        self._score_plans.pop(key, None)
+        self._score_plans[key] = True
+        self.plan(wins, Lc["heads"])
+        while len(self._score_plans) > self.SCORE_PLANS_KEPT:
+            self._tiles.pop(next(iter(self._score_plans)), None)
+            del self._score_plans[next(iter(self._score_plans))]
+        x = torch.empty((L, Lc["hidden"]), dtype=torch.float32, device=self.dev)
+        self.embed(ids, x)
+        kv_rows = torch.arange(prefix_len, prefix_len + L, dtype=torch.int32, device=self.dev)
+        h = self.llm_forward(x, 0, pos, kv_rows, cache, prefix_len, causal=False, und_rounding=1, final_norm_dtype=torch.bfloat16,
+                             windows=wins)
+        cache.length = prefix_len                            # the scored rows were never part of the scene
+        logits = torch.empty((L, Lc["vocab"]), dtype=torch.bfloat16, device=self.dev)
+        hip.linear(h, self.w["lm_head"], out=logits)
+        lp = torch.empty(L, dtype=torch.float32, device=self.dev)
+        rank = torch.empty(L, dtype=torch.int32, device=self.dev)
+        hip.logprob_rows_bf16(logits, targets, rank=rank, out=lp)
+        return lp, rank
 
     # ------------------------------------------------------------------ DINOv2 encoder
     def dino_embed(self, images_norm):

@@ -99,6 +99,8 @@ _SIGS = {
     "g2v_kv_quant_e4m3": ([_P, _L, _I, _P, _P, _P], C.c_int),
     "g2v_kv_dequant_e4m3": ([_P, _P, _L, _I, _P, _P], C.c_int),
     "g2v_decode_attn_pg_kv8": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P], C.c_int),
+    "g2v_logprob_rows_workspace": ([_I, _I], C.c_int64),
+    "g2v_logprob_rows_bf16": ([_P, _I, _I, _L, _P, _P, _P, _P, _P, _L, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -838,6 +840,43 @@ def sample_rows_bf16(x, out, scratch, rng):
         x = x.view(1, -1)
     _ck(lib().g2v_sample_rows_bf16(_p(x), x.shape[0], x.shape[1], _rowmajor(x), _p(out), _p(scratch), _p(rng), _stream()),
         "g2v_sample_rows_bf16")
+    return out
+
+
+_logprob_scratch = {}
+LOGPROB_WS_WORDS = 1 << 16
+
+
+def logprob_rows_workspace(rows, n):
+    """Bytes of scratch with which g2v_logprob_rows_bf16 deals the rows of a [rows, n] launch out to several workgroups each
+    (0: it would not)."""
+    return int(lib().g2v_logprob_rows_workspace(int(rows), int(n)))
+
+
+def logprob_rows_bf16(logits, targets, lse=None, rank=None, out=None, scratch=None):
+    """out[r] = log_softmax(logits[r].float(), -1)[targets[r]] (g2v_logprob_rows_bf16): logits bf16 [rows, n] (row stride >= n),
+    targets int32 [rows]; lse fp32 [rows] / rank int32 [rows], when given, receive the row's logsumexp and the target's rank
+    (0: the argmax).  A target outside [0, n) gives NaN and rank -1.  Returns out (fp32 [rows], allocated when None).
+    scratch: int32, zeroed once, >= logprob_rows_workspace(rows, n) bytes when the caller owns one (a captured graph must not
+    allocate); else one per scratch_owner, as the argmax ticket.  The results do not depend on it.
+    A row whose entries are all -inf gives -inf for both (torch: NaN)."""
+    rows, n = logits.shape
+    assert logits.dtype == torch.bfloat16 and targets.dtype == torch.int32 and targets.numel() == rows and targets.is_contiguous()
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    assert out.dtype == torch.float32 and out.numel() == rows and out.is_contiguous()
+    assert lse is None or (lse.dtype == torch.float32 and lse.numel() == rows and lse.is_contiguous())
+    assert rank is None or (rank.dtype == torch.int32 and rank.numel() == rows and rank.is_contiguous())
+    if scratch is None and logprob_rows_workspace(rows, n):
+        # one per scratch_owner, allocated once at a fixed size and never replaced (a captured graph keeps its pointer): 256 KiB
+        # cover 511 rows of the 151 936-entry vocabulary (118 KB); a launch that would need more gets none and runs one
+        # workgroup per row, which gives the same bits
+        key = scratch_owner(logits.device.index)
+        scratch = _logprob_scratch.get(key)
+        if scratch is None:
+            scratch = _logprob_scratch[key] = torch.zeros(LOGPROB_WS_WORDS, dtype=torch.int32, device=logits.device)
+    _ck(lib().g2v_logprob_rows_bf16(_p(logits), rows, n, _rowmajor(logits), _p(targets), _p(out), _p(lse), _p(rank), _p(scratch),
+                                    scratch.numel() * 4 if scratch is not None else 0, _stream()), "g2v_logprob_rows_bf16")
     return out
 
 

@@ -15,7 +15,7 @@ import os
 import torch
 
 from ... import hip, host
-from ...engine import Engine
+from ...engine import Engine, pack_continuations
 from ...weights import Weights
 from .qwen2vl import NaiveCache
 
@@ -548,6 +548,77 @@ class G2VLM:
         ids = self.generate_text(past_key_values=past, max_length=max_length, do_sample=do_sample, temperature=temperature,
                                  end_token_id=new_token_ids["eos_token_id"], **gi)
         return tokenizer.decode(ids[1:, 0])
+
+    # ---- scoring: how likely is a given answer (multiple choice, reranking, confidence)
+    def _check_continuations(self, continuations, what):
+        """The continuations as lists of ints, or ValueError: 1..64 of them, each at least one id of the vocabulary, and no
+        more rows in all than one scoring pass takes."""
+        conts = [[int(t) for t in c] for c in continuations]
+        if not 1 <= len(conts) <= Engine.SCORE_MAX_SEGMENTS:
+            raise ValueError(f"{what}: 1..{Engine.SCORE_MAX_SEGMENTS} candidates, got {len(conts)}")
+        vocab = self.dims["llm"]["vocab"]
+        for j, c in enumerate(conts):
+            if not c:
+                raise ValueError(f"{what}: candidate {j} has no tokens")
+            if min(c) < 0 or max(c) >= vocab:
+                raise ValueError(f"{what}: candidate {j} holds a token id outside [0, {vocab})")
+        rows = sum(len(c) for c in conts)
+        if rows > Engine.SCORE_MAX_ROWS:
+            raise ValueError(f"{what}: {rows} tokens in all, one scoring pass takes at most {Engine.SCORE_MAX_ROWS}")
+        return conts
+
+    @torch.no_grad()
+    def score_continuations(self, past_key_values, start_inputs, continuations):
+        """Log-probabilities of given continuations after a prefill.  past_key_values / start_inputs: exactly what
+        generate_text would be given (the pair _chat_prefill returns).  continuations: 1..64 lists of token ids, each of at
+        least one id and at most Engine.SCORE_MAX_ROWS ids in all (ValueError otherwise).  Continuation c is scored as
+        generate_text would have produced it: the input rows are [start, c0 .. c_{n-2}] at positions pos, pos + 1, .., the
+        targets are c.  All continuations go through the und expert in one teacher-forced pass (Engine.score_rows).
+        Returns one dict per continuation: `logprobs` fp32 [n] (log_softmax of the bf16 logits, fp32 arithmetic), `ranks`
+        int32 [n] (0: the token greedy decode would have picked) and `total`, the sum of logprobs as a Python float.
+        The cache is unchanged on return (same length, same bits in its rows), so generate_text or another
+        score_continuations can follow on it.  decode_weights and decode_kv have no effect here: scoring is a prefill, and
+        prefills stay bf16."""
+        conts = self._check_continuations(continuations, "score_continuations")
+        gi = start_inputs
+        assert gi["packed_start_tokens"].numel() == 1 and past_key_values.length == int(_cpu(gi["key_values_lens"]).sum())
+        start, pos = int(_cpu(gi["packed_start_tokens"])[0]), int(_cpu(gi["packed_query_position_ids"])[0, 0])
+        ids, poss, seg_lens, targets = pack_continuations(start, pos, conts)
+        lp, rank = self.engine.score_rows(past_key_values, past_key_values.length, self._dev_i32(torch.tensor(ids)),
+                                          self._dev_i32(torch.tensor(poss).expand(3, -1)), seg_lens, self._dev_i32(torch.tensor(targets)))
+        lp, rank = lp.cpu(), rank.cpu()                       # the one wait, after the pass
+        out, off = [], 0
+        for n in seg_lens:
+            out.append(dict(logprobs=lp[off:off + n].clone(), ranks=rank[off:off + n].clone(), total=float(lp[off:off + n].double().sum())))
+            off += n
+        return out
+
+    @torch.no_grad()
+    def chat_with_recon_choices(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt, choices,
+                                append_eos=True, normalize=False):
+        """Multiple choice over one scene: prefill as chat_with_recon does, then score every string of `choices` as the
+        assistant's answer - tokenised with add_special_tokens=False, followed by eos_token_id when append_eos - in one pass
+        (score_continuations).  Returns (best_index, scores, details): scores[j] is choice j's total log-probability, divided
+        by its number of tokens when `normalize`; details[j] its score_continuations dict plus `ids`.  Ties go to the lower
+        index.  ValueError, before the prefill, for an empty list, more than 64 choices, or a choice that tokenises to nothing.
+        decode_weights and decode_kv have no effect here."""
+        choices = list(choices)
+        if not 1 <= len(choices) <= Engine.SCORE_MAX_SEGMENTS:
+            raise ValueError(f"chat_with_recon_choices: 1..{Engine.SCORE_MAX_SEGMENTS} choices, got {len(choices)}")
+        conts = []
+        for j, text in enumerate(choices):
+            ids = [int(t) for t in tokenizer.encode(text, add_special_tokens=False)]
+            if not ids:
+                raise ValueError(f"chat_with_recon_choices: choice {j} ({text!r}) tokenises to nothing")
+            conts.append(ids + ([int(new_token_ids["eos_token_id"])] if append_eos else []))
+        conts = self._check_continuations(conts, "chat_with_recon_choices")
+        past, gi = self._chat_prefill(tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt)
+        details = self.score_continuations(past, gi, conts)
+        for d, c in zip(details, conts):
+            d["ids"] = c
+        scores = [d["total"] / len(c) if normalize else d["total"] for d, c in zip(details, conts)]
+        best = max(range(len(scores)), key=lambda j: (scores[j], -j))
+        return best, scores, details
 
     # ---- batched decode: several scenes answered together (SURVEY 8f-3; the reference is batch 1, g2vlm.py:1006, 1137)
     @torch.no_grad()

@@ -356,6 +356,25 @@ int g2v_decode_attn_pg_kv8(const void* qkv, const void* q_norm_w, const void* k_
                            const void* cos, const void* sin, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
                            void* out, const void* Lk_dev, int batch, int64_t scene_rows, int max_len, int Hq, int Hkv,
                            float scale, void* workspace, void* stream);
+
+/* ---- scoring (csrc/logprob.hip): log-probability of a given token per row of logits ------------------------------------------
+ * log_softmax(x.float(), -1)[target] per row of bf16 x[rows, ld >= n]; targets int32 [rows] on the device.
+ * out_lp   fp32 [rows]  : x[t] - max - log(sum exp(x - max)), fp32 arithmetic
+ * out_lse  fp32 [rows]  or NULL : max + log(sum exp(x - max))
+ * out_rank int32 [rows] or NULL : #{i : x[i] > x[t]} + #{i < t : x[i] == x[t]} (0: what g2v_argmax_rows_bf16 picks on a NaN-free row)
+ * A target outside [0, n) gives out_lp = NaN and out_rank = -1; nothing is read out of range, and columns [n, ld) are never read.
+ * -inf entries contribute 0, a -inf target gives -inf - also in a row whose n entries are all -inf, whose logsumexp is -inf
+ * (torch gives NaN there); a difference x[t] - max beyond the fp32 range gives -inf.
+ * One pass over the row, 16-byte loads where the row's base allows them.  A row's three results depend on its n elements and
+ * its target only - not on rows, on its position, on the alignment of its base or on `scratch` - bit for bit.
+ * scratch: NULL, or int32 words zeroed ONCE by the caller (the kernel resets its tickets), >= g2v_logprob_rows_workspace(rows, n)
+ * bytes: with it, the rows of a launch too small to fill the chip are each dealt out to several workgroups; without it (or
+ * with too little) every row is one workgroup's.  The workspace size is 0 where no split would be made.  hipGraph-capturable.
+ * (The entry point was proposed as (x, rows, n, ld, targets, out_lp, out_lse, out_rank, stream); scratch, scratch_bytes and
+ * g2v_logprob_rows_workspace are added to it because the library owns no device memory: the caller does, per scratch owner.) */
+int64_t g2v_logprob_rows_workspace(int rows, int n);
+int g2v_logprob_rows_bf16(const void* x, int rows, int n, int64_t ld, const void* targets, void* out_lp, void* out_lse,
+                          void* out_rank, void* scratch, int64_t scratch_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

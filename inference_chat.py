@@ -15,6 +15,8 @@ parser.add_argument("--decode-weights", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the decode step streams its Linear weights as e4m3 with one power-of-two scale per row")
 parser.add_argument("--decode-kv", choices=("bf16", "fp8"), default="bf16",
                     help="fp8: the decode step keeps its KV cache as e4m3 with one power-of-two scale per row and kv head")
+parser.add_argument("--choices", nargs="+", default=None, metavar="ANSWER",
+                    help="score these candidate answers (log-likelihood, one pass) and print the most likely one instead of generating")
 
 
 def main(argv=None):
@@ -33,6 +35,14 @@ def main(argv=None):
         templated = args.question
     images = [Image.open(args.image_path).convert("RGB")]
     images, conversation = process_conversation(images, templated)
+    if args.choices:
+        best, scores, details = model.chat_with_recon_choices(tokenizer, new_token_ids, image_transform, dino_transform, images=images,
+                                                              prompt=conversation, choices=args.choices)
+        print(f"{'choice':<24} {'tokens':>6} {'log-prob':>10} {'per token':>10}  first-token rank")
+        for text, score, d in zip(args.choices, scores, details):
+            print(f"{text[:24]:<24} {len(d['ids']):>6} {score:>10.4f} {score / len(d['ids']):>10.4f}  {int(d['ranks'][0])}")
+        print("answer: ", args.choices[best])
+        return args.choices[best]
     response = model.chat_with_recon(tokenizer, new_token_ids, image_transform, dino_transform, images=images,
                                      prompt=conversation, max_length=100)
     print("answer: ", response)
