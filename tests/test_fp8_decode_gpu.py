@@ -20,12 +20,10 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import gemm_check as G  # noqa: E402
-from g2vlm_amd.quant import dequantize_rows, quantize_rows_e4m3  # noqa: E402
-from g2vlm_amd.weights import interleave_gate_up  # noqa: E402
+import decode_check as D  # noqa: E402
+from decode_check import Case  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-EPS = 1e-6
 MEASURED = {}
 
 
@@ -58,91 +56,14 @@ def rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def nan_bf16(*shape):
-    return torch.full(shape, G.NAN_BF16, dtype=torch.int16, device="cuda").view(torch.bfloat16)
-
-
-_EYE = {}
-
-
-def normalised_rows(hip, xf, nw):
-    """bf16 [B, K]: the rows the fused-norm kernels multiply, read back through the bf16 gemv_pg norm form and an identity."""
-    K = xf.shape[1]
-    if K not in _EYE:
-        _EYE[K] = torch.eye(K, dtype=torch.bfloat16, device="cuda")
-    out = torch.empty(xf.shape, dtype=torch.bfloat16, device="cuda")
-    for b in range(xf.shape[0]):
-        hip.gemv_pg(xf[b], _EYE[K], norm_w=nw, eps=EPS, out=out[b])
-    return out
-
-
-class Case:
-    """Operands of one form.  form: 'qkv' (fp32 residual row, RMSNorm, bias, bf16 out), 'o' / 'down' (bf16 x, fp32 residual
-    add), 'gu' (RMSNorm, interleaved gate/up rows, SwiGLU), 'lm' (RMSNorm, bf16 out), 'bias' (bf16 x, bias, bf16 out)."""
-
-    def __init__(self, form, B, N, K, seed):
-        self.form, self.B, self.N, self.K = form, B, N, K
-        self.norm = form in ("qkv", "gu", "lm")
-        self.act = form == "gu"
-        w = rnd(N, K, seed=seed, scale=K ** -0.5)
-        if form == "gu":
-            w = interleave_gate_up(w[:N // 2].contiguous(), w[N // 2:].contiguous())
-        if form == "lm":
-            w = w * torch.exp(2.0 * rnd(N, seed=seed + 5)).unsqueeze(1)     # heavy-tailed row scales (synth.peaked_lm_head)
-        q, s = quantize_rows_e4m3(w.bfloat16())
-        self.q, self.s, self.wd = dev(q), dev(s), dev(dequantize_rows(q, s))
-        self.bias = dev(rnd(N, seed=seed + 1, scale=0.1).bfloat16()) if form in ("qkv", "bias") else None
-        self.nw = dev(1 + 0.1 * rnd(K, seed=seed + 2)) if self.norm else None
-        self.x = dev(rnd(B, K, seed=seed + 3)) if self.norm else dev(rnd(B, K, seed=seed + 3).bfloat16())
-        self.res0 = dev(rnd(B, N, seed=seed + 4)) if form in ("o", "down") else None
-        self.n_out = N // 2 if self.act else N
-
-    def target(self):
-        if self.res0 is not None:
-            return self.res0.clone()
-        return nan_bf16(self.B, self.n_out)
-
-    def kw(self, tgt):
-        k = dict(norm_w=self.nw, eps=EPS if self.norm else 0.0, bias=self.bias, act=self.act)
-        k["res" if self.res0 is not None else "out"] = tgt
-        return k
-
-    def run_fp8(self, hip, batched):
-        tgt = self.target()
-        if batched:
-            hip.gemv_pg_batch_fp8(self.x, self.q, self.s, **self.kw(tgt))
-        else:
-            for b in range(self.B):
-                hip.gemv_pg_fp8(self.x[b], self.q, self.s, **self.kw(tgt[b]))
-        torch.cuda.synchronize()
-        return tgt
-
-    def run_bf16(self, hip, batched):
-        tgt = self.target()
-        if batched:
-            hip.gemv_pg_batch(self.x, self.wd, **self.kw(tgt))
-        else:
-            for b in range(self.B):
-                hip.gemv_pg(self.x[b], self.wd, **self.kw(tgt[b]))
-        torch.cuda.synchronize()
-        return tgt
-
-    def check(self, hip, got):
-        A = normalised_rows(hip, self.x, self.nw) if self.norm else self.x
-        epi = G.EPI_SWIGLU if self.act else (G.EPI_RES_F32 if self.res0 is not None else G.EPI_BF16)
-        return G.check_gemm(got, A, self.wd, self.bias, epi, res=self.res0)
+def record(name, chk):
+    D.record(name, chk, store=MEASURED)
 
 
 REAL = [("qkv", 2048, 1536), ("o", 1536, 1536), ("gu", 17920, 1536), ("down", 1536, 8960), ("lm", 151936, 1536)]
 RAGGED = [("qkv", 7, 256), ("qkv", 300, 1536), ("lm", 1000, 256), ("gu", 96, 256), ("gu", 992, 1536),
           ("o", 7, 256), ("o", 300, 2064), ("o", 1000, 9216), ("down", 7, 9216), ("down", 300, 8960), ("down", 1000, 2064),
           ("bias", 7, 2064), ("bias", 1000, 256), ("bias", 300, 9216)]
-
-
-def record(name, chk, extra=""):
-    m = MEASURED.setdefault(name, dict(n=0, multi=0, max_ulps=0.0, max_d=0.0))
-    m["n"] += chk.n; m["multi"] += chk.multi
-    m["max_ulps"] = max(m["max_ulps"], chk.max_ulps); m["max_d"] = max(m["max_d"], chk.max_d)
 
 
 @pytest.mark.parametrize("form,N,K", REAL + RAGGED, ids=lambda v: str(v))
