@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512) void gemv_pg_kernel(const void* xin, const flo
 // xor butterfly 8, 4, 2, 1): the appended K row and the scores are bit-identical to the separate kernels.
 __global__ __launch_bounds__(256, 2) void decode_attn_pg_kernel(AttnArgs a G2V_STAMP_ARG) {
   __shared__ AttnLds lds;
-  decode_attn_pg_body<false, false, 4>(a, lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, threadIdx.x G2V_STAMP_PASS_DEV);
+  decode_attn_pg_body<KvBf16>(a, lds, blockIdx.x, blockIdx.y, blockIdx.z, gridDim.x, threadIdx.x G2V_STAMP_PASS_DEV);
 }
 
 template <int XMODE, bool ACT, int KCH>
@@ -264,8 +264,8 @@ extern "C" int g2v_decode_attn_pg(const void* qkv, const void* q_norm_w, const v
     return G2V_ERR_ARG;
   const int nbh = decode_attn_pg_nbh(Hkv, batch);
   AttnArgs a{(const __bf16*)qkv, (const float*)q_norm_w, (const float*)k_norm_w, (const float*)cos, (const float*)sin, eps, und_rounding,
-             (__bf16*)k_cache, (__bf16*)v_cache, (float*)workspace, (const int*)Lk_dev, Hq, Hkv, scale, (long)scene_rows, max_len, (max_len + nbh - 1) / nbh,
-             ((max_len + nbh - 1) / nbh + 3) / 4};
+             k_cache, v_cache, (float*)workspace, (const int*)Lk_dev, Hq, Hkv, scale, (long)scene_rows, max_len, (max_len + nbh - 1) / nbh,
+             ((max_len + nbh - 1) / nbh + 3) / 4, nullptr, nullptr};
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(decode_attn_pg_kernel, dim3(nbh, Hkv, batch), dim3(256), 0, s, a G2V_STAMP_PASS);
   G2V_CHECK_LAUNCH();

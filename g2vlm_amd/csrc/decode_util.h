@@ -1,4 +1,5 @@
-// Lane-level helpers shared by the decode-step kernels (decode_layer.hip, decode_batch.hip).
+// Lane-level helpers and the in-kernel stamp macros shared by the decode kernels: decode_layer.hip, decode_batch.hip,
+// decode_fp8.hip, decode_kv8.hip, decode_shared.hip and logprob.hip (three of them through decode_attn_pg.h as well).
 #pragma once
 #include "common.h"
 
@@ -7,6 +8,7 @@
 #ifdef G2V_STAMPS
 #define G2V_STAMP_ARG , unsigned long long* dbg
 #define G2V_STAMP_PASS , g_stamp_buf
+#define G2V_STAMP_PASS_NONE , (unsigned long long*)nullptr   // a launch from a file without the stamp buffer: its kernel records nothing
 #define G2V_STAMP_PASS_DEV , dbg
 #define G2V_STAMP(i)                                                                                                   \
   do {                                                                                                                 \
@@ -29,6 +31,7 @@
 #else
 #define G2V_STAMP_ARG
 #define G2V_STAMP_PASS
+#define G2V_STAMP_PASS_NONE
 #define G2V_STAMP_PASS_DEV
 #define G2V_STAMP(i)
 #define G2V_STAMP_RT(i)
@@ -53,6 +56,10 @@ __device__ __forceinline__ float row16_sum(float x) {
   x += dpp_f<0x124>(x);                                     // row_ror:4: lane ^ 4 up to the ^8 the first step made equal
   x += dpp_f<0x122>(x);
   x += dpp_f<0x121>(x);
+  return x;
+}
+__device__ __forceinline__ float row16_max(float x) {
+  x = fmaxf(x, dpp_f<0x128>(x)); x = fmaxf(x, dpp_f<0x124>(x)); x = fmaxf(x, dpp_f<0x122>(x)); x = fmaxf(x, dpp_f<0x121>(x));
   return x;
 }
 

@@ -241,6 +241,17 @@ def test_attn_pg_in_the_engine_s_form_appends_and_matches_fp64(hip, Hq, B, shift
     check_step(hip, slot_lengths(B, shift), Hq, 2, seed=100 * B + 10 * shift + Hq)
 
 
+GROUPS = [(2, 2, 0), (3, 1, 3), (8, 2, 6), (8, 1, 1)]         # (Hq, Hkv, shift): G = 1, 3, 4, 8 - one, one, two and three passes of
+#                                                              four rows over the G + 1 rows to normalise, and GMAX
+
+
+@pytest.mark.parametrize("Hq,Hkv,shift", GROUPS)
+def test_attn_pg_at_the_edges_of_the_group_size(hip, Hq, Hkv, shift):
+    """G = 1, 3, 4, 8 at B = 3 (G = 6 and 2 above): the same assertions and bounds, which are on the error against fp64 and do not
+    depend on G."""
+    check_step(hip, slot_lengths(3, shift), Hq, Hkv, seed=300 + 10 * shift + Hq + Hkv)
+
+
 @pytest.mark.parametrize("Hq", [12, 4])
 def test_attn_pg_with_a_full_slot_and_with_idle_waves(hip, Hq):
     """Lk == max_len (the new row is the bucket's last); max_len = 130 at B = 1: S = 2 keys per block, SW = 1 per wave, so waves

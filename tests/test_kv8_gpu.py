@@ -190,6 +190,13 @@ def test_kv8_attention_appends_quantised_and_matches_fp64(hip, Hq, B, shift):
     check_step(hip, slot_lengths(B, shift), Hq, 2, seed=100 * B + 10 * shift + Hq)
 
 
+@pytest.mark.parametrize("Hq,Hkv,shift", [(2, 2, 0), (3, 1, 3), (8, 2, 6), (8, 1, 1)])
+def test_kv8_attention_at_the_edges_of_the_group_size(hip, Hq, Hkv, shift):
+    """G = 1, 3, 4, 8 at B = 3: one to three passes of four rows over the G + 1 rows to normalise, and GMAX.  The same assertions
+    and bounds as above: they are on the error against fp64 and do not depend on G."""
+    check_step(hip, slot_lengths(3, shift), Hq, Hkv, seed=300 + 10 * shift + Hq + Hkv)
+
+
 def test_kv8_attention_streams_five_batches_and_rescales(hip):
     """B = 8 at 17 000 rows: 32 blocks per kv head and scene, 534 keys per block, 134 per wave."""
     check_step(hip, [17000, 4103, 33, 357, 2, 17000, 1, 65], 12, 2, seed=17)

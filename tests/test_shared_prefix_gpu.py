@@ -60,7 +60,16 @@ def run_shared(hip, s, plen, Hq, Hkv, smax=SMAX):
 @pytest.mark.parametrize("B", [1, 5, 6, 16])
 @pytest.mark.parametrize("plen", [1, 31, 33, 4103, 17000])
 def test_shared_prefix_attention_matches_fp64_and_the_concatenated_cache(hip, Hq, B, plen):
-    Hkv = 2
+    check_shared(hip, Hq, 2, B, plen)
+
+
+@pytest.mark.parametrize("Hq,Hkv,plen", [(2, 2, 33), (3, 1, 4103), (8, 2, 31), (8, 1, 4103)])
+def test_shared_prefix_attention_at_the_edges_of_the_group_size(hip, Hq, Hkv, plen):
+    """G = 1, 3, 4, 8 at B = 3 (32, 10, 8 and 4 slots per column group): the same assertions and bounds, which do not depend on G."""
+    check_shared(hip, Hq, Hkv, 3, plen)
+
+
+def check_shared(hip, Hq, Hkv, B, plen):
     G = Hq // Hkv
     s = make_step(hip, B, plen, Hq, Hkv, seed=plen + 7 * B + Hq)
     kp0, vp0, ks0, vs0 = s["kp"].clone(), s["vp"].clone(), s["ks"].clone(), s["vs"].clone()
