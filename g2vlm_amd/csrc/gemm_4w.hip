@@ -24,30 +24,17 @@
 //
 // Same math, epilogues, grouping (und / geo experts) and bf16 rounding points as gemm.hip / gemm_8p.hip (reference: every
 // nn.Linear under autocast, e.g. modeling/qwen2vl/modeling_qwen2_vl.py:508-521, modeling/g2vlm/qwen2vl.py:579-606).
-#include <type_traits>
-#include <utility>
-#include "common.h"
+//
+// This file: the four-wave main loop, its DMA geometry, fragment code and accumulator registers.  Kernel arguments, LDS
+// geometry, tile walk, epilogue (it reads the accumulators through acc_get) and the persistent launcher are shared with
+// gemm_8p.hip: gemm_tile256.h; gemm_8p.hip packs the arguments and picks the form.
+#include "gemm_tile256.h"
 #include "lds_dma.h"
-#include "g2vlm_hip.h"
 #include "gemm_internal.h"
 
 namespace {
 
-constexpr int BN = 256, BK = 64, NT = 256;
-constexpr int BM_MAX = 288;
-constexpr int OP_BYTES = BM_MAX * 128;                   // A tile: up to 288 rows x 128 B; the 256-row B tile follows it
-constexpr int KBUF_BYTES = OP_BYTES + 256 * 128;         // A + B = 68 KiB per K-tile slot, two slots
-constexpr int OUT_PITCH = 256 * 2 + 16;                  // epilogue staging: bf16 [rows][256], rows padded by 16 B
-constexpr int LDS_BYTES = KBUF_BYTES + 160 * OUT_PITCH;  // the epilogue image (<= 160 rows per pass) sits above ring slot 0
-
-struct W4Group {
-  const __bf16* A; const __bf16* W; const __bf16* bias; void* C; const void* res; const float* gamma;
-  int M, tile_start;
-};
-struct W4Args {
-  W4Group g[2];
-  int ngroups, N, K, lda, ldc, ldres, tiles_n, flags, sm, sn, total;
-};
+constexpr int NT = 256;                                 // four waves
 
 // the K-tile bases are formed by SALU adds from per-tile bases (no VALU-written SGPR): only the M0 write needs its wait state
 #ifdef EXP_4W_NO_READS
@@ -60,11 +47,6 @@ struct W4Args {
 #else
 #define DMA16 dma16_saddr_settled
 #endif
-
-template <class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) { sfor_impl(f, std::make_integer_sequence<int, N>{}); }
 
 // The accumulators live in a0 .. a255, OWNED by this file: hipcc cannot be made to keep 256 accumulator registers in AGPRs
 // beside 200 VGPRs of fragments (builtin MFMAs: 2.8 v_accvgpr moves per MFMA and scratch spills in the main loop), so the
@@ -89,7 +71,7 @@ __device__ __forceinline__ void mfma_vacc(f32x4& c, const bf16x8& b, const bf16x
 }
 
 template <int EPI, int MA0, int MA1>
-__global__ __launch_bounds__(NT, 1) void gemm4w_kernel(W4Args a) {
+__global__ __launch_bounds__(NT, 1) void gemm4w_kernel(T256Args a) {
   static_assert(MA0 + MA1 <= 9, "256 accumulator AGPRs + 32 VGPRs");
   acc_declare();
   constexpr int MT = MA0 + MA1;                            // 16-row m-fragments per wave
@@ -130,29 +112,10 @@ __global__ __launch_bounds__(NT, 1) void gemm4w_kernel(W4Args a) {
     int gi, m0, n0;
     uint32_t a_src[2][MAX_MA], b_src[2][4];                // per-lane byte offsets from the tile's first A row / W row
   };
-  // tile id -> context: XCD-aware bijective remap, then supertile walk (as gemm_8p.hip)
+  // tile id -> context (gemm_tile256.h: XCD remap, supertile walk)
   auto setup_tile = [&](int vt, TileCtx& c) {
-    const int nwg = a.total;
-    int bid = vt;
-    {
-      int xcd = bid & 7, qn = nwg >> 3, rn = nwg & 7;
-      bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (bid >> 3);
-    }
-    c.gi = (a.ngroups > 1 && bid >= a.g[1].tile_start) ? 1 : 0;
+    tile_origin<BMv>(a, vt, c.gi, c.m0, c.n0);
     const int gM = a.g[c.gi].M;
-    const int t_id = bid - a.g[c.gi].tile_start;
-    int tm, tn;
-    {
-      const int tiles_m = (gM + BMv - 1) / BMv;
-      const int row_sz = a.sm * a.tiles_n;
-      int sup_m = t_id / row_sz, r = t_id - sup_m * row_sz;
-      int h = min(a.sm, tiles_m - sup_m * a.sm);
-      int full_w = a.sn * h;
-      int sup_n = r / full_w, p = r - sup_n * full_w;
-      tm = sup_m * a.sm + p % h;                           // walk down the column first: consecutive tiles share the W slab
-      tn = sup_n * a.sn + p / h;
-    }
-    c.m0 = tm * BMv; c.n0 = tn * BN;
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
@@ -188,8 +151,8 @@ __global__ __launch_bounds__(NT, 1) void gemm4w_kernel(W4Args a) {
   setup_tile(blockIdx.x, cur);
   bool prefetched = false;                                 // K-tile 0 of `cur` is already in flight / landed in slot 0
   for (int vt = blockIdx.x; vt < a.total; vt += gridDim.x) {
-  const W4Group g = a.g[cur.gi];
-  const int m0 = cur.m0, n0 = cur.n0, M = g.M;
+  const T256Group g = a.g[cur.gi];
+  const int m0 = cur.m0, n0 = cur.n0;
   const char* Ab = uniform_ptr(reinterpret_cast<const char*>(g.A + (size_t)m0 * a.lda));
   const char* Wb = uniform_ptr(reinterpret_cast<const char*>(g.W + (size_t)n0 * K));
   const int nk = K / BK;
@@ -341,7 +304,7 @@ __global__ __launch_bounds__(NT, 1) void gemm4w_kernel(W4Args a) {
   const bool has_next = vn < a.total;
   if (has_next) {
     setup_tile(vn, cur);                                   // m0 / n0 / g of the tile being finished are in locals
-    const W4Group& gn_ = a.g[cur.gi];
+    const T256Group& gn_ = a.g[cur.gi];
     const char* An = uniform_ptr(reinterpret_cast<const char*>(gn_.A + (size_t)cur.m0 * a.lda));
     const char* Wn = uniform_ptr(reinterpret_cast<const char*>(gn_.W + (size_t)cur.n0 * K));
     sfor<4>([&](auto c) { stage_half(0, c, An, Wn, cur.a_src, cur.b_src); });
@@ -352,215 +315,36 @@ __global__ __launch_bounds__(NT, 1) void gemm4w_kernel(W4Args a) {
   prefetched = has_next;
   continue;
 #endif
-  // ------------------------------------------------------------------ epilogue (gemm_8p.hip's, for 4 waves x 128 columns)
-  // Two passes over the m-fragments (i < I0, then the rest), each: (1) every lane rounds its accumulators to the bf16 Linear
-  // output (bias, activation) and writes them, 4 consecutive columns = 8 bytes at a time, into a row-major bf16 image in LDS;
-  // (2) the block walks that image in 16-byte chunks, 32 (16 for SwiGLU) consecutive lanes per output row: every global
-  // access - output store, residual load - is a full 16-byte lane access on 512 (256) contiguous bytes per row.
-  constexpr bool SWI = EPI == G2V_EPI_SWIGLU;
-  constexpr int PITCH = OUT_PITCH;
-  constexpr int I0 = (MT + 1) / 2;                         // m-fragments per pass
-  constexpr int CPR = SWI ? 16 : 32;                       // 16-byte chunks per output row
-  constexpr int RPI = NT / CPR;                            // rows per sweep
-  char* const img = smem + KBUF_BYTES;
-  int etid = tid;
-  asm volatile("" : "+v"(etid));
-  const int efr = etid & 15, efq = (etid >> 4) & 3;
-  const int ch = etid % CPR, r0 = etid / CPR;
-  const int gn = (SWI ? (n0 >> 1) : n0) + ch * 8;          // first of this lane's 8 output columns
-  const bool round_gamma = a.flags & G2V_GEMM_GAMMA_ROUND_BF16;
-  sfor<2>([&](auto h_) {
-    constexpr int h = h_;
-    const int irow0 = wr * 16 * I0 + efr;
-    if constexpr (SWI) {
-      sfor<I0>([&](auto ii_) {
-        constexpr int ii = ii_, i = h * I0 + ii;
-        if constexpr (i < MT) {
-          sfor<4>([&](auto jp_) {
-            constexpr int jp = jp_;
-            float o[4];
-            sfor<4>([&](auto r_) {
-              constexpr int r = r_;
-              float gt = bfround(acc_get(std::integral_constant<int, i>{}, std::integral_constant<int, 2 * jp>{}, r_));
-              float up = bfround(acc_get(std::integral_constant<int, i>{}, std::integral_constant<int, 2 * jp + 1>{}, r_));
-              float sl = bfround(siluf_(gt));
-              o[r] = sl * up;
-            });
-            *reinterpret_cast<u32x2*>(img + (irow0 + ii * 16) * PITCH + (wc * 64 + jp * 16 + efq * 4) * 2) =
-                u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-          });
-        }
-      });
-    } else {
-      sfor<8>([&](auto j_) {
-        constexpr int j = j_;
-        const int cl = wc * 128 + j * 16 + efq * 4;
-        float bv[4] = {0.f, 0.f, 0.f, 0.f};
-        if (g.bias) {
-          u32x2 bb = *reinterpret_cast<const u32x2*>(g.bias + n0 + cl);
-          bv[0] = bits2f_lo(bb[0]); bv[1] = bits2f_hi(bb[0]); bv[2] = bits2f_lo(bb[1]); bv[3] = bits2f_hi(bb[1]);
-        }
-        sfor<I0>([&](auto ii_) {
-          constexpr int ii = ii_, i = h * I0 + ii;
-          if constexpr (i < MT) {
-            float o[4];
-            sfor<4>([&](auto r_) {
-              constexpr int r = r_;
-              float v = bfround(acc_get(std::integral_constant<int, i>{}, j_, r_) + bv[r]);
-              if constexpr (EPI == G2V_EPI_GELU) v = gelu_fast(v);
-              if constexpr (EPI == G2V_EPI_QUICKGELU) {
-                float u = bfround(1.702f * v);
-                float sg = bfround(sigmoidf_(u));
-                v = v * sg;
-              }
-              o[r] = v;
-            });
-            *reinterpret_cast<u32x2*>(img + (irow0 + ii * 16) * PITCH + cl * 2) = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
-          }
-        });
-      });
-    }
-    float gam[8];
-    bool has_gam = false;
-    if constexpr (EPI == G2V_EPI_RES_F32) {
-      has_gam = g.gamma != nullptr;
-      if (has_gam) {
-        f32x4 g0 = *reinterpret_cast<const f32x4*>(g.gamma + gn), g1 = *reinterpret_cast<const f32x4*>(g.gamma + gn + 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { gam[e] = g0[e]; gam[4 + e] = g1[e]; }
-      }
-    }
-    __syncthreads();
-    // sweep in batches: residual loads and LDS reads of a batch are all issued before the first store waits on them
-    constexpr int NIT = 2 * 16 * I0 / RPI;
-    constexpr int SB = NIT % 5 == 0 ? 5 : (NIT % 4 == 0 ? 4 : (NIT % 3 == 0 ? 3 : 2));
-    static_assert(NIT % SB == 0, "sweep batches");
-#pragma unroll
-    for (int it0 = 0; it0 < NIT; it0 += SB) {
-      u32x4 pk[SB];
-      int gmv[SB];
-      bool ok[SB];
-      [[maybe_unused]] f32x4 ra[SB], rb[SB];
-      [[maybe_unused]] u32x4 rr[SB];
-#pragma unroll
-      for (int c = 0; c < SB; ++c) {
-        const int irow = (it0 + c) * RPI + r0;
-        const int iwr = irow / (16 * I0), rem = irow - iwr * (16 * I0);
-        const int trow = h * 16 * I0 + rem;                // row inside the wave row
-        gmv[c] = m0 + iwr * HB + trow;
-        ok[c] = trow < HB && gmv[c] < M;
-        if constexpr (EPI == G2V_EPI_RES_F32) {
-          ra[c] = rb[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (ok[c] && g.res) {
-            const float* rp = reinterpret_cast<const float*>(g.res) + (size_t)gmv[c] * a.ldres + gn;
-            ra[c] = *reinterpret_cast<const f32x4*>(rp); rb[c] = *reinterpret_cast<const f32x4*>(rp + 4);
-          }
-        } else if constexpr (EPI == G2V_EPI_RES_BF16) {
-          rr[c] = u32x4{0u, 0u, 0u, 0u};
-          if (ok[c]) rr[c] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const __bf16*>(g.res) + (size_t)gmv[c] * a.ldres + gn);
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < SB; ++c) pk[c] = *reinterpret_cast<const u32x4*>(img + ((it0 + c) * RPI + r0) * PITCH + ch * 16);
-#pragma unroll
-      for (int c = 0; c < SB; ++c) {
-        if (!ok[c]) continue;
-        const int gm = gmv[c];
-        if constexpr (EPI == G2V_EPI_RES_F32) {
-          float v[8];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { v[2 * e] = bits2f_lo(pk[c][e]); v[2 * e + 1] = bits2f_hi(pk[c][e]); }
-          if (has_gam) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              v[e] = __fmul_rn(v[e], gam[e]);
-              if (round_gamma) v[e] = bfround(v[e]);
-            }
-          }
-          float* cp = reinterpret_cast<float*>(g.C) + (size_t)gm * a.ldc + gn;
-          *reinterpret_cast<f32x4*>(cp) = f32x4{__fadd_rn(ra[c][0], v[0]), __fadd_rn(ra[c][1], v[1]), __fadd_rn(ra[c][2], v[2]), __fadd_rn(ra[c][3], v[3])};
-          *reinterpret_cast<f32x4*>(cp + 4) = f32x4{__fadd_rn(rb[c][0], v[4]), __fadd_rn(rb[c][1], v[5]), __fadd_rn(rb[c][2], v[6]), __fadd_rn(rb[c][3], v[7])};
-        } else if constexpr (EPI == G2V_EPI_RES_BF16) {
-          u32x4 ov;
-#pragma unroll
-          for (int e = 0; e < 4; ++e)
-            ov[e] = pack_bf16x2(bits2f_lo(rr[c][e]) + bits2f_lo(pk[c][e]), bits2f_hi(rr[c][e]) + bits2f_hi(pk[c][e]));
-          *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.C) + (size_t)gm * a.ldc + gn) = ov;
-        } else {
-          *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(g.C) + (size_t)gm * a.ldc + gn) = pk[c];
-        }
-      }
-    }
-    __syncthreads();                                      // the image is dead: the second pass / the next tile's DMA may overwrite it
-  });
+  tile_epilogue<EPI, MT, NT, 8>(a, g, smem, tid, wr, wc, m0, n0, acc_get);
   prefetched = has_next;
   }
 }
 
 template <int EPI, int MA0, int MA1>
-int launch_h(const W4Args& a, int total, hipStream_t s) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(gemm4w_kernel<EPI, MA0, MA1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            LDS_BYTES) != hipSuccess) return G2V_ERR_LAUNCH;
-    attr_set = true;
-  }
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return G2V_ERR_LAUNCH;
-    n_cu = prop.multiProcessorCount & ~7;                  // multiple of 8: a workgroup keeps its XCD group across tiles
-    if (n_cu <= 0) n_cu = 256;
-  }
-  W4Args b = a;
-  b.total = total;
-  hipLaunchKernelGGL((gemm4w_kernel<EPI, MA0, MA1>), dim3(total < n_cu ? total : n_cu), dim3(NT), LDS_BYTES, s, b);
-  G2V_CHECK_LAUNCH();
-  return G2V_OK;
-}
+int launch_h(const T256Args& a, hipStream_t s) { return launch_persistent<gemm4w_kernel<EPI, MA0, MA1>, NT>(a, s); }
 
 template <int EPI>
-int launch(const W4Args& a, int bm, int total, hipStream_t s) {
-  if (bm == 288) return launch_h<EPI, 5, 4>(a, total, s);
+int launch(const T256Args& a, int bm, hipStream_t s) {
+  if (bm == 288) return launch_h<EPI, 5, 4>(a, s);
 #ifndef G2V_4W_FEW                                           // G2V_4W_FEW: tests/test_build_cpu.py audits a subset of the instantiations
-  if (bm == 256) return launch_h<EPI, 4, 4>(a, total, s);
-  if (bm == 224) return launch_h<EPI, 4, 3>(a, total, s);
-  if (bm == 192) return launch_h<EPI, 4, 2>(a, total, s);
+  if (bm == 256) return launch_h<EPI, 4, 4>(a, s);
+  if (bm == 224) return launch_h<EPI, 4, 3>(a, s);
+  if (bm == 192) return launch_h<EPI, 4, 2>(a, s);
 #endif
-  if (bm == 160) return launch_h<EPI, 3, 2>(a, total, s);
-  return launch_h<EPI, 2, 2>(a, total, s);
+  if (bm == 160) return launch_h<EPI, 3, 2>(a, s);
+  return launch_h<EPI, 2, 2>(a, s);
 }
 
 }  // namespace
 
-// Same eligibility as gemm_8p.hip (g2v_gemm_8p_supported); the tile height is chosen there and handed over.
-int g2v_gemm_4w_launch(const g2v_gemm_desc* d, int bm, const int* order, hipStream_t s) {
-  W4Args a;
-  a.ngroups = 0; a.N = d->N; a.K = d->K; a.lda = d->lda; a.ldc = d->ldc; a.ldres = d->ldres;
-  a.tiles_n = d->N / BN; a.flags = d->flags;
-  a.sn = a.tiles_n < 8 ? a.tiles_n : 8;
-  a.sm = 32 / a.sn > 1 ? 32 / a.sn : 1;
-  int total = 0;
-  for (int i = 0; i < d->ngroups; ++i) {
-    const g2v_gemm_group& sg = d->g[order[i]];
-    if (sg.M <= 0) continue;
-    W4Group& g = a.g[a.ngroups++];
-    g.A = (const __bf16*)sg.A; g.W = (const __bf16*)sg.W; g.bias = (const __bf16*)sg.bias; g.C = sg.C; g.res = sg.res;
-    g.gamma = (const float*)sg.gamma; g.M = sg.M; g.tile_start = total;
-    total += ((sg.M + bm - 1) / bm) * a.tiles_n;
-  }
-  if (a.ngroups == 1) a.g[1] = a.g[0];
-  if (total == 0) return G2V_OK;
-  switch (d->epilogue) {
-#ifndef G2V_4W_FEW
-    case G2V_EPI_BF16: return launch<G2V_EPI_BF16>(a, bm, total, s);
-    case G2V_EPI_GELU: return launch<G2V_EPI_GELU>(a, bm, total, s);
-    case G2V_EPI_QUICKGELU: return launch<G2V_EPI_QUICKGELU>(a, bm, total, s);
-    case G2V_EPI_RES_BF16: return launch<G2V_EPI_RES_BF16>(a, bm, total, s);
+// Same eligibility as gemm_8p.hip (g2v_gemm_8p_supported); the arguments are packed and the tile height is chosen there.
+int g2v_gemm_4w_launch(const T256Args& a, int epilogue, int bm, hipStream_t s) {
+  return g2v_gemm_with_epilogue(epilogue, [&](auto epi) {
+    constexpr int EPI = decltype(epi)::value;
+#ifdef G2V_4W_FEW
+    if constexpr (EPI != G2V_EPI_SWIGLU && EPI != G2V_EPI_RES_F32) return G2V_ERR_ARG; else
 #endif
-    case G2V_EPI_SWIGLU: return launch<G2V_EPI_SWIGLU>(a, bm, total, s);
-    case G2V_EPI_RES_F32: return launch<G2V_EPI_RES_F32>(a, bm, total, s);
-    default: return G2V_ERR_ARG;
-  }
+    return launch<EPI>(a, bm, s);
+  });
 }
+

@@ -13,7 +13,7 @@ Section 1 (test_form_*, test_skinny_*, test_two_groups_*, test_ab_loops): each f
 last row tile at M - m0 in {1, HB-1, HB, HB+1, bm-1, bm} for every tile height of the 8-wave and 4-wave forms (HB = bm/2, a
 wave row; the MFMA skip of gemm_8p.hip), the 64-row wave boundaries and N / K tails of the 128x128 kernel, M % 32 tails of
 the big tile, the skinny kernel's m-tile switches and its cross-workgroup K split, two-group launches, lda > K, ldc > N,
-ldres > N and in-place residuals.  g2v_gemm_route must report the form each case claims.
+ldres > N and in-place residuals; test_form_256_persistent_two_groups: two groups with more tiles than CUs.  g2v_gemm_route must report the form each case claims.
 Section 2 (test_production): each production call site at its engine shape, grouping and aliasing through the default
 dispatcher: the route it takes is asserted (ROUTES, table below), and five launches are bit-identical.
 Section 3: gemm_f32 at the head shapes: |got - ref| <= K 2^-24 (|A|.|W|^T + |b|) + 2^-23 |ref| per element.
@@ -376,6 +376,26 @@ def test_two_groups(hip, form):
                     assert r[0] == form, (form, Ms, r)
                 L.run(fl)
                 L.check(form, (r[1], 256), f"{form} groups {Ms} {epi_name}")
+
+
+@pytest.mark.parametrize("form", ["8p", "4w"])
+def test_form_256_persistent_two_groups(hip, form):
+    """The persistent tile loop of the 256-column forms at its smallest: two groups with more 128-row tiles than the chip has
+    CUs (8 tile columns; 128 ceil(CUs / 8) + 1 rows, so the last tile row holds one row, beside a 6-row group), either order,
+    so a workgroup finishes a tile of one group with the first K-tile of a tile of the other group already in flight.  SwiGLU
+    and the in-place fp32 residual with gamma."""
+    n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+    fl = hip.FORCE_8P | (hip.P8_EIGHT_WAVES if form == "8p" else hip.P8_FOUR_WAVES) | hip.P8_H128
+    rows = (128 * ((n_cu + 7) // 8) + 1, 6)
+    assert (sum((m + 127) // 128 for m in rows)) * 8 > n_cu
+    for order in ((0, 1), (1, 0)):
+        Ms = [rows[o] for o in order]
+        for epi_name in ("swiglu", "res_f32_gamma_inplace"):
+            epi, kw = EPIS[epi_name]
+            L = Launch(hip, epi, Ms, 2048, 128, lda_pad=64, ldc_pad=16, seed=170 + order[0], **kw)
+            expect_route(L.route(fl), form, 128)
+            L.run(fl)
+            L.check(form, (128, 256), f"{form} persistent groups {Ms} {epi_name}")
 
 
 def test_sensitivity_one_zeroed_element(hip):
