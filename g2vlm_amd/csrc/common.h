@@ -79,4 +79,15 @@ __device__ __forceinline__ float gelu_fast(float x) {
   return 0.5f * x * (1.0f + er);
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float siluf_(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }   // callers round to bf16
+// Callers round to bf16.  The fast form: below x = -87.3 its 1 + exp(-x) exceeds 2^126, v_rcp_f32 flushes the subnormal
+// reciprocal and the result is -0 where silu(x) ~ x exp(x) is still a normal float (-5.3e-37 at x = -88).  The GEMM tile
+// epilogues use it as it is: a guard there costs 4 % of the SwiGLU GEMM's time (measured), and their check carries an absolute
+// floor of 2^-30 T_gate T_up (tests/gemm_check.py) that is thirty orders of magnitude above the flushed value.
+__device__ __forceinline__ float siluf_fast_(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// The decode kernels (memory-bound GEMVs) and swiglu_bf16, which are bit-identical to each other and checked against fp64
+// with a relative bound only, take that rare tail through x exp(x + 44) * exp(-44): every caller passes a bf16-rounded
+// gate, so x + 44 is exact, and x exp(x + 44) stays normal.
+__device__ __forceinline__ float siluf_(float x) {
+  if (__builtin_expect(x < -87.f, 0)) return (x * expf(x + 44.f)) * 7.781132241133797e-20f;
+  return siluf_fast_(x);
+}

@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmArgs a) {
           if (gm >= M) continue;
           float gt = bfround(acc[i][2 * jp][r]);
           float up = bfround(acc[i][2 * jp + 1][r]);
-          float s = bfround(siluf_(gt));
+          float s = bfround(siluf_fast_(gt));
           C[(size_t)gm * a.ldc + oc] = f2bf(s * up);
         }
       }

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(512) void gemm_skinny_kernel(SkArgs a) {
     if constexpr (EPI == G2V_EPI_SWIGLU) {
       const int oc = blockIdx.x * 16 + nl;
       float gt = bfround(v0), up = bfround(v1);
-      float sl = bfround(siluf_(gt));
+      float sl = bfround(siluf_fast_(gt));
       reinterpret_cast<__bf16*>(a.C)[(size_t)m * a.ldc + oc] = f2bf(sl * up);
     } else {
       const int gn = blockIdx.x * 16 + nl;

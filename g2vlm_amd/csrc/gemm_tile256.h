@@ -115,7 +115,7 @@ __device__ __forceinline__ void tile_epilogue(const T256Args& a, const T256Group
               constexpr int r = r_;
               float gt = bfround(acc(std::integral_constant<int, i>{}, std::integral_constant<int, 2 * jp>{}, r_));
               float up = bfround(acc(std::integral_constant<int, i>{}, std::integral_constant<int, 2 * jp + 1>{}, r_));
-              float sl = bfround(siluf_(gt));
+              float sl = bfround(siluf_fast_(gt));
               o[r] = sl * up;
             });
             *reinterpret_cast<u32x2*>(img + (irow0 + ii * 16) * PITCH + (wc * NJ * 8 + jp * 16 + efq * 4) * 2) =

@@ -328,17 +328,24 @@ __global__ __launch_bounds__(512) void camera_tail_kernel(const float* feat, int
   }
 }
 
-// argmax over bf16 logits (first maximal index): 64 blocks reduce slices to (value, index) pairs, the last block to
+// argmax over bf16 logits (first maximal index): 64 blocks reduce slices to (key, index) pairs, the last block to
 // arrive (atomic ticket) reduces the 64 partials.  scratch: int32[1 + 2*64] zeroed once by the caller (ticket is reset).
-// NaN ranks above everything (torch.argmax returns the index of a NaN), so the result is ALWAYS an index of the input:
-// a decode loop that feeds it to an embedding gather must not be able to leave the table.
-__device__ __forceinline__ void argmax_merge(float& best, int& bi, float ov, int oi) {
-  if (ov != ov) ov = INFINITY;
-  if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; }
+// Values are merged as ordered integer keys (argmax_key): monotone in the float, -0 == +0, every NaN on top - above +inf,
+// as torch.argmax ranks it - so the first NaN of a row wins, else the first maximal index.  The result is ALWAYS an index
+// of the input: a decode loop that feeds it to an embedding gather must not be able to leave the table.
+constexpr int ARGMAX_KEY_NAN = 0x7fffffff;
+constexpr int ARGMAX_KEY_NONE = (int)0x80000000;          // below -inf's key: "no candidate yet"
+__device__ __forceinline__ int argmax_key(float v) {
+  const int b = __float_as_int(v);
+  const int k = b >= 0 ? b : (b ^ 0x7fffffff);            // negative floats: larger magnitude, smaller key (-0 -> -1, -inf -> 0x807fffff)
+  return v != v ? ARGMAX_KEY_NAN : (v == 0.f ? 0 : k);
+}
+__device__ __forceinline__ void argmax_merge(int& best, int& bi, int ok, int oi) {
+  if (ok > best || (ok == best && oi < bi)) { best = ok; bi = oi; }
 }
 
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so every (row, index) of every decode step draws its own number
-// with no state shared between lanes; the host restatement in tests/test_kernels_gpu.py reproduces it bit for bit.
+// with no state shared between lanes; the host restatement in tests/imageop_check.py reproduces it bit for bit.
 __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -358,14 +365,14 @@ __device__ __forceinline__ uint32_t philox_first(uint32_t c0, uint32_t c1, uint3
 // finishes a row's reduction bumps nothing: the step counter is advanced by rng_step_kernel (launched behind the draw by g2v_sample_rows_bf16: one writer per step).
 template <bool SAMPLE>
 __global__ __launch_bounds__(256) void argmax_bf16_kernel(const __bf16* x, int n, int* out, int* scratch, long ld, const int* rng) {
-  __shared__ float sv[4];
+  __shared__ int sv[4];
   __shared__ int si[4];
   __shared__ int last;
   const int nb = gridDim.x;
   x += (size_t)blockIdx.y * ld;
   out += blockIdx.y;
   scratch += blockIdx.y * 129;
-  float best = -INFINITY;
+  int best = ARGMAX_KEY_NONE;
   int bi = 0x7fffffff;                                     // "no candidate yet": loses every tie; replaced below if still unset
   const int per = (n + nb - 1) / nb, lo = blockIdx.x * per, hi = min(n, lo + per);
   if constexpr (SAMPLE) {
@@ -374,10 +381,10 @@ __global__ __launch_bounds__(256) void argmax_bf16_kernel(const __bf16* x, int n
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
       const uint32_t r = philox_first((uint32_t)i, blockIdx.y, step, 0u, k0, k1);
       const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);          // 24 bits, strictly inside (0, 1)
-      argmax_merge(best, bi, bf2f(x[i]) * inv_t - logf(-logf(u)), i);
+      argmax_merge(best, bi, argmax_key(bf2f(x[i]) * inv_t - logf(-logf(u))), i);
     }
   } else {
-    for (int i = lo + threadIdx.x; i < hi; i += 256) argmax_merge(best, bi, bf2f(x[i]), i);
+    for (int i = lo + threadIdx.x; i < hi; i += 256) argmax_merge(best, bi, argmax_key(bf2f(x[i])), i);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
@@ -386,7 +393,7 @@ __global__ __launch_bounds__(256) void argmax_bf16_kernel(const __bf16* x, int n
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int k = 1; k < 4; ++k) argmax_merge(best, bi, sv[k], si[k]);
-    __hip_atomic_store(reinterpret_cast<float*>(scratch + 1) + 2 * blockIdx.x, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(scratch + 1 + 2 * blockIdx.x, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(scratch + 2 + 2 * blockIdx.x, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -396,9 +403,9 @@ __global__ __launch_bounds__(256) void argmax_bf16_kernel(const __bf16* x, int n
   __syncthreads();
   if (last && threadIdx.x < 64) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    float b2 = -INFINITY; int i2 = 0x7fffffff;
+    int b2 = ARGMAX_KEY_NONE, i2 = 0x7fffffff;
     if ((int)threadIdx.x < nb) {
-      b2 = __hip_atomic_load(reinterpret_cast<float*>(scratch + 1) + 2 * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      b2 = __hip_atomic_load(scratch + 1 + 2 * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       i2 = __hip_atomic_load(scratch + 2 + 2 * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #pragma unroll

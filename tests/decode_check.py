@@ -160,7 +160,9 @@ class Case:
         self.bias = dev(rnd(N, seed=seed + 1, scale=0.1).bfloat16()) if form in ("qkv", "bias") else None
         self.nw = dev(1 + 0.1 * rnd(K, seed=seed + 2)) if self.norm else None
         if form == "sw":
-            self.x = dev(rnd(B, 2 * K, seed=seed + 3).bfloat16())
+            x = rnd(B, 2 * K, seed=seed + 3)
+            x[:, 0] = -88.0                                      # gate 0 (its up value is x[:, 16]): silu's flushed-reciprocal tail
+            self.x = dev(x.bfloat16())
         else:
             self.x = dev(rnd(B, K, seed=seed + 3)) if self.norm else dev(rnd(B, K, seed=seed + 3).bfloat16())
         self.res0 = dev(rnd(B, N, seed=seed + 4)) if form in RES_FORMS else None

@@ -5,6 +5,8 @@ with a rel-L2 bound and a max error of a couple of bf16 ulps (fp32 accumulation 
 between an MFMA tile loop and a CPU GEMM, which can flip a final bf16 rounding).
 """
 import math
+import os
+import sys
 
 import numpy as np
 
@@ -14,6 +16,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from oracle import g2vlm_oracle as O  # noqa: E402  (checker only)
 
 
@@ -987,24 +990,7 @@ def test_decode_attn_fused_is_bit_identical_to_separate_kernels(hip):
 
 
 # ----------------------------------------------------------------------------------------- sampling (do_sample)
-def philox_first(c0, c1, c2, c3, k0, k1):
-    """Philox4x32-10, first output word; numpy uint64 arithmetic restating csrc/misc.hip::philox_first."""
-    M0, M1, W0, W1, MASK = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85, 0xFFFFFFFF
-    c0, c1, c2, c3 = (np.asarray(v, dtype=np.uint64) & MASK for v in np.broadcast_arrays(c0, c1, c2, c3))
-    k0, k1 = np.uint64(k0 & MASK), np.uint64(k1 & MASK)
-    for _ in range(10):
-        p0, p1 = np.uint64(M0) * c0, np.uint64(M1) * c2
-        h0, l0, h1, l1 = p0 >> np.uint64(32), p0 & MASK, p1 >> np.uint64(32), p1 & MASK
-        c0, c1, c2, c3 = (h1 ^ c1 ^ k0) & MASK, l1, (h0 ^ c3 ^ k1) & MASK, l0
-        k0, k1 = (k0 + np.uint64(W0)) & MASK, (k1 + np.uint64(W1)) & MASK
-    return c0
-
-
-def gumbel_scores(logits_f32, inv_t, seed, step, row):
-    n = logits_f32.shape[0]
-    r = philox_first(np.arange(n), row, step, 0, seed & 0xFFFFFFFF, seed >> 32)
-    u = ((r >> np.uint64(8)).astype(np.float64) + 0.5) / 16777216.0
-    return logits_f32.astype(np.float64) * inv_t - np.log(-np.log(u))
+from imageop_check import gumbel_scores, philox_first  # noqa: E402,F401  (the host restatement of csrc/misc.hip::philox_first)
 
 
 @pytest.mark.parametrize("n", [500, 151936])
