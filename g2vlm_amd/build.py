@@ -17,7 +17,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libg2vlm_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_8p.hip", "gemm_4w.hip", "gemm_skinny.hip", "attn.hip", "norm_rope.hip", "misc.hip", "decode.hip",
-           "decode_layer.hip", "decode_batch.hip", "decode_shared.hip", "decode_fp8.hip", "decode_kv8.hip", "logprob.hip"]
+           "decode_layer.hip", "decode_batch.hip", "decode_shared.hip", "decode_fp8.hip", "decode_kv8.hip", "logprob.hip", "topk.hip"]
 
 
 # per-source flags.  attn.hip: hipcc's SLP vectoriser packs neighbouring f32 adds / multiplies of the softmax into v_pk_*_f32,
@@ -33,7 +33,8 @@ FILE_FLAGS = {"attn.hip": ["-fno-slp-vectorize"]}
 # decode_kv8.hip: the attention on an e4m3 cache holds a batch as codes AND as converted fragments; no scratch, <= 256 VGPRs
 # (tests/test_kv8_cpu.py)
 # logprob.hip: a lane holds 32 logits of a chunk between its max pass and its exp pass; no scratch (tests/test_score_cpu.py)
-RESOURCE_AUDIT = ("gemm_4w.hip", "attn.hip", "decode_fp8.hip", "decode_kv8.hip", "logprob.hip")
+# topk.hip: a lane holds the 32 keys of a chunk through its selection rounds; no scratch (tests/test_score_questions_cpu.py)
+RESOURCE_AUDIT = ("gemm_4w.hip", "attn.hip", "decode_fp8.hip", "decode_kv8.hip", "logprob.hip", "topk.hip")
 
 
 def resources_path(src, objdir=None):

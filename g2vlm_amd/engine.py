@@ -81,10 +81,62 @@ def score_windows(prefix_len, seg_lens):
     return tuple(wins)
 
 
+def pack_questions(questions):
+    """Rows of scoring the choices of several questions about one scene in one pass.  questions[j] = (text_ids, text_pos,
+    start_token, start_pos, continuations): the ids and mRoPE positions of question j's own text rows behind the scene (what
+    _chat_question prefills), the start token and position generate_text would be given behind them, and the choices as
+    lists of token ids.  Rows [0, Lq): every question's text rows, one question after the other; rows [Lq, L): question by
+    question, every choice as pack_continuations lays it out behind that question's start token.
+    Returns (ids [L], positions [L], layout, targets [L - Lq]); layout[j] = (text rows of question j, (rows of each of its
+    choices)).  Only the choice rows have targets."""
+    ids, poss, layout, tail_ids, tail_pos, targets = [], [], [], [], [], []
+    for text_ids, text_pos, start_token, start_pos, continuations in questions:
+        text_ids, text_pos = [int(t) for t in text_ids], [int(p) for p in text_pos]
+        if not text_ids or len(text_ids) != len(text_pos):
+            raise ValueError("a question needs at least one text row, and one position per row")
+        if len(continuations) < 1:
+            raise ValueError("a question without a choice has nothing to score")
+        ids += text_ids
+        poss += text_pos
+        c_ids, c_pos, seg_lens, c_tg = pack_continuations(start_token, start_pos, continuations)
+        tail_ids += c_ids
+        tail_pos += c_pos
+        targets += c_tg
+        layout.append((len(text_ids), tuple(seg_lens)))
+    return ids + tail_ids, poss + tail_pos, tuple(layout), targets
+
+
+def question_windows(prefix_len, layout):
+    """Attention windows (q0, q_len, k0, k_len, causal) of pack_questions' rows over a scene of prefix_len cache rows; row r's
+    K/V sit at cache row prefix_len + r.  Question j, rows [a, a + m): the scene (every key) and, causally, itself - what its
+    own prefill behind the scene sees.  Choice c of question j, rows [b, b + n): the scene, question j's rows (every key) and,
+    causally, itself - what score_windows gives it over a cache that ends with question j.  Nothing sees another question or
+    another choice.  Windows that share their query rows are merged by the attention plan's combine pass."""
+    P = int(prefix_len)
+    wins, a, starts = [], 0, []
+    for m, _ in layout:
+        if P > 0:
+            wins.append((a, m, 0, P, False))
+        wins.append((a, m, P + a, m, True))
+        starts.append(a)
+        a += m
+    b = a
+    for (m, seg_lens), a_j in zip(layout, starts):
+        for n in seg_lens:
+            if P > 0:
+                wins.append((b, n, 0, P, False))
+            wins.append((b, n, P + a_j, m, False))
+            wins.append((b, n, P + b, n, True))
+            b += n
+    return tuple(wins)
+
+
 class Engine(Decode):
     SCORE_MAX_ROWS = 8192        # rows of one score_rows pass: its logits are rows x vocab bf16 (2.5 GB at the real vocabulary)
     SCORE_MAX_SEGMENTS = 64
     SCORE_PLANS_KEPT = 32        # attention plans of score_rows kept (one per (prefix_len, seg_lens)); the oldest is dropped beyond
+    SCORE_MAX_QUESTIONS = 64     # questions of one score_questions pass, each with 1..SCORE_MAX_SEGMENTS choices ...
+    SCORE_MAX_CHOICES = 1024     # ... and this many choices in all
 
     def __init__(self, weights, dims):
         self.w = weights
@@ -318,7 +370,7 @@ class Engine(Decode):
         return hip.gather_rows(self.w["embed"], ids_i32, out)
 
     # ------------------------------------------------------------------ scoring: log-probabilities of given continuations
-    def score_rows(self, cache, prefix_len, ids, pos, seg_lens, targets):
+    def score_rows(self, cache, prefix_len, ids, pos, seg_lens, targets, top_k=0):
         """Log-probabilities of C given continuations of one prefilled scene, all in ONE teacher-forced pass.
 
         cache: the scene's KVCache, cache.length == prefix_len.  ids int32 [L], pos int32 [3, L], targets int32 [L] on the
@@ -330,39 +382,97 @@ class Engine(Decode):
         On return cache.length is prefix_len again and rows [0, prefix_len) keep their bits (a cache too small for prefix_len
         + L rows is reallocated and copied, as by any prefill, and stays grown: at most SCORE_MAX_ROWS rows per scene cache).
         This is a prefill: it reads the bf16 weights and the bf16 cache with the prefill kernels whatever decode_weights and
-        decode_kv are set to."""
-        Lc = self.dims["llm"]
+        decode_kv are set to.
+        top_k > 0 (at most 32): the logprob launch also writes the rows' logsumexp and ONE g2v_topk_rows_bf16 launch on the same
+        logits follows; returns (log-probability, rank, logsumexp fp32 [L], top ids int32 [L, top_k], top logits fp32 [L,
+        top_k]) - entry j of a row is the token whose rank is j, its log-probability is top logit - logsumexp."""
         L = int(sum(seg_lens))
         if not 1 <= len(seg_lens) <= self.SCORE_MAX_SEGMENTS or min(seg_lens) < 1:
             raise ValueError(f"score_rows: 1..{self.SCORE_MAX_SEGMENTS} continuations of at least one token each")
         if L > self.SCORE_MAX_ROWS:
             raise ValueError(f"score_rows: {L} rows in one pass, at most {self.SCORE_MAX_ROWS}")
+        self._check_top_k(top_k, "score_rows")
         assert cache.length == prefix_len and ids.numel() == L and targets.numel() == L and tuple(pos.shape) == (3, L)
         wins = score_windows(prefix_len, seg_lens)
-        # the plan is built (and uploaded) before the first launch.  An evaluation sweep brings a new (prefix_len, seg_lens) with
-        # nearly every item, so only the SCORE_PLANS_KEPT most recently used ones stay (their device tables are freed in stream
-        # order, behind the launches that read them).  The plan cache is keyed by (windows, heads) alone, so evicting also drops
-        # the plan of another caller that happens to use the identical windows; that caller rebuilds it on its next call -
-        # a little host work, never a wrong result
-        key = (wins, Lc["heads"])
+        self._score_plan(wins)
+        return self._score_pass(cache, prefix_len, ids, pos, wins, 0, targets, top_k)
+
+    def _score_plan(self, wins):
+        """The attention plan of a scoring pass, built (and uploaded) before the first launch.  An evaluation sweep brings a new
+        shape with nearly every item, so only the SCORE_PLANS_KEPT most recently used ones stay (their device tables are freed
+        in stream order, behind the launches that read them).  The plan cache is keyed by (windows, heads) alone, so evicting
+        also drops the plan of another caller that happens to use the identical windows; that caller rebuilds it on its next
+        call - a little host work, never a wrong result."""
+        key = (wins, self.dims["llm"]["heads"])
         self._score_plans.pop(key, None)
         self._score_plans[key] = True
-        self.plan(wins, Lc["heads"])
+        self.plan(wins, key[1])
         while len(self._score_plans) > self.SCORE_PLANS_KEPT:
             self._tiles.pop(next(iter(self._score_plans)), None)
             del self._score_plans[next(iter(self._score_plans))]
+
+    def _score_pass(self, cache, prefix_len, ids, pos, wins, first, targets, top_k):
+        """One teacher-forced pass of L rows behind the scene under `wins`; logits, log-probabilities, ranks and (top_k > 0)
+        the top-k entries of the rows [first, L) only."""
+        Lc = self.dims["llm"]
+        L = ids.numel()
         x = torch.empty((L, Lc["hidden"]), dtype=torch.float32, device=self.dev)
         self.embed(ids, x)
         kv_rows = torch.arange(prefix_len, prefix_len + L, dtype=torch.int32, device=self.dev)
         h = self.llm_forward(x, 0, pos, kv_rows, cache, prefix_len, causal=False, und_rounding=1, final_norm_dtype=torch.bfloat16,
                              windows=wins)
         cache.length = prefix_len                            # the scored rows were never part of the scene
-        logits = torch.empty((L, Lc["vocab"]), dtype=torch.bfloat16, device=self.dev)
-        hip.linear(h, self.w["lm_head"], out=logits)
-        lp = torch.empty(L, dtype=torch.float32, device=self.dev)
-        rank = torch.empty(L, dtype=torch.int32, device=self.dev)
-        hip.logprob_rows_bf16(logits, targets, rank=rank, out=lp)
-        return lp, rank
+        n = L - first
+        logits = torch.empty((n, Lc["vocab"]), dtype=torch.bfloat16, device=self.dev)
+        hip.linear(h[first:] if first else h, self.w["lm_head"], out=logits)
+        lp = torch.empty(n, dtype=torch.float32, device=self.dev)
+        rank = torch.empty(n, dtype=torch.int32, device=self.dev)
+        if not top_k:
+            hip.logprob_rows_bf16(logits, targets, rank=rank, out=lp)
+            return lp, rank
+        lse = torch.empty(n, dtype=torch.float32, device=self.dev)
+        hip.logprob_rows_bf16(logits, targets, lse=lse, rank=rank, out=lp)
+        top_ids = torch.empty((n, int(top_k)), dtype=torch.int32, device=self.dev)
+        top_vals = torch.empty((n, int(top_k)), dtype=torch.float32, device=self.dev)
+        hip.topk_rows_bf16(logits, int(top_k), out_idx=top_ids, out_val=top_vals)
+        return lp, rank, lse, top_ids, top_vals
+
+    def score_questions(self, cache, prefix_len, ids, pos, layout, targets, top_k=0):
+        """score_rows for the choices of Q questions about one prefilled scene, questions included, in ONE teacher-forced pass.
+
+        cache: the scene's KVCache (system prompt, views, images - no question), cache.length == prefix_len.  ids int32 [L],
+        pos int32 [3, L], layout and targets int32 [L - Lq] as pack_questions lays them out: the Lq text rows of all questions
+        first, then every choice's rows.  All L rows go through one llm_forward on the und expert under question_windows'
+        attention (a question sees the scene and itself, a choice the scene, its question and itself), their K/V in cache rows
+        [prefix_len, prefix_len + L) beyond the cache's length; the bf16 final norm of the choice rows alone - the contiguous
+        tail - feeds ONE lm_head GEMM, ONE g2v_logprob_rows_bf16 launch and, with top_k > 0, ONE g2v_topk_rows_bf16 launch.
+        Returns what score_rows returns, for the L - Lq choice rows.  Nothing waits for the device; on return cache.length is
+        prefix_len and the scene's rows keep their bits.  1..SCORE_MAX_QUESTIONS questions of 1..SCORE_MAX_SEGMENTS choices,
+        SCORE_MAX_CHOICES choices and SCORE_MAX_ROWS rows in all (ValueError before any launch)."""
+        layout = tuple((int(m), tuple(int(n) for n in segs)) for m, segs in layout)
+        if not 1 <= len(layout) <= self.SCORE_MAX_QUESTIONS:
+            raise ValueError(f"score_questions: 1..{self.SCORE_MAX_QUESTIONS} questions, got {len(layout)}")
+        for m, segs in layout:
+            if m < 1 or not 1 <= len(segs) <= self.SCORE_MAX_SEGMENTS or min(segs) < 1:
+                raise ValueError(f"score_questions: a question of at least one row with 1..{self.SCORE_MAX_SEGMENTS} choices of at "
+                                 "least one token each")
+        n_choices = sum(len(segs) for _, segs in layout)
+        if n_choices > self.SCORE_MAX_CHOICES:
+            raise ValueError(f"score_questions: {n_choices} choices in one pass, at most {self.SCORE_MAX_CHOICES}")
+        Lq = sum(m for m, _ in layout)
+        L = Lq + sum(sum(segs) for _, segs in layout)
+        if L > self.SCORE_MAX_ROWS:
+            raise ValueError(f"score_questions: {L} rows in one pass, at most {self.SCORE_MAX_ROWS}")
+        self._check_top_k(top_k, "score_questions")
+        assert cache.length == prefix_len and ids.numel() == L and targets.numel() == L - Lq and tuple(pos.shape) == (3, L)
+        wins = question_windows(prefix_len, layout)
+        self._score_plan(wins)
+        return self._score_pass(cache, prefix_len, ids, pos, wins, Lq, targets, top_k)
+
+    @staticmethod
+    def _check_top_k(top_k, what):
+        if not 0 <= int(top_k) <= hip.TOPK_MAX:
+            raise ValueError(f"{what}: top_k = {top_k}, 0 (none) .. {hip.TOPK_MAX}")
 
     # ------------------------------------------------------------------ DINOv2 encoder
     def dino_embed(self, images_norm):

@@ -101,6 +101,8 @@ _SIGS = {
     "g2v_decode_attn_pg_kv8": ([_P, _P, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _I, _I, _F, _P, _P], C.c_int),
     "g2v_logprob_rows_workspace": ([_I, _I], C.c_int64),
     "g2v_logprob_rows_bf16": ([_P, _I, _I, _L, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_topk_rows_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_topk_rows_bf16": ([_P, _I, _I, _L, _I, _P, _P, _P, _L, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -878,6 +880,45 @@ def logprob_rows_bf16(logits, targets, lse=None, rank=None, out=None, scratch=No
     _ck(lib().g2v_logprob_rows_bf16(_p(logits), rows, n, _rowmajor(logits), _p(targets), _p(out), _p(lse), _p(rank), _p(scratch),
                                     scratch.numel() * 4 if scratch is not None else 0, _stream()), "g2v_logprob_rows_bf16")
     return out
+
+
+_topk_scratch = {}
+TOPK_MAX = 32                                               # G2V_TOPK_MAX
+TOPK_WS_WORDS = 1 << 17                                     # 512 KiB: every split launch (< 512 rows, k <= 32) fits
+
+
+def topk_rows_workspace(rows, n, k):
+    """Bytes of scratch with which g2v_topk_rows_bf16 deals the rows of a [rows, n] launch out to several workgroups each
+    (0: it would not)."""
+    return int(lib().g2v_topk_rows_workspace(int(rows), int(n), int(k)))
+
+
+def topk_rows_bf16(logits, k, out_idx=None, out_val=None, scratch=None):
+    """The first k entries of every row of bf16 logits [rows, n] (row stride >= n) in argmax_rows_bf16's order - larger first,
+    -0 == +0, NaN on top, equal values by ascending index (g2v_topk_rows_bf16): returns (idx int32 [rows, k], val fp32
+    [rows, k]), allocated when None; idx[:, 0] is the argmax, val the selected elements themselves.  k > n leaves index -1 /
+    value NaN behind the n entries.  1 <= k <= 32.
+    scratch: int32, zeroed once, >= topk_rows_workspace(rows, n, k) bytes when the caller owns one (a captured graph must not
+    allocate); else one per scratch_owner, as logprob_rows_bf16's.  The results do not depend on it."""
+    rows, n = logits.shape
+    k = int(k)
+    assert logits.dtype == torch.bfloat16
+    if not 1 <= k <= TOPK_MAX:
+        raise ValueError(f"topk_rows_bf16: k = {k}, 1..{TOPK_MAX}")
+    if out_idx is None:
+        out_idx = torch.empty((rows, k), dtype=torch.int32, device=logits.device)
+    if out_val is None:
+        out_val = torch.empty((rows, k), dtype=torch.float32, device=logits.device)
+    assert out_idx.dtype == torch.int32 and tuple(out_idx.shape) == (rows, k) and out_idx.is_contiguous()
+    assert out_val.dtype == torch.float32 and tuple(out_val.shape) == (rows, k) and out_val.is_contiguous()
+    if scratch is None and topk_rows_workspace(rows, n, k):
+        key = scratch_owner(logits.device.index)
+        scratch = _topk_scratch.get(key)
+        if scratch is None:
+            scratch = _topk_scratch[key] = torch.zeros(TOPK_WS_WORDS, dtype=torch.int32, device=logits.device)
+    _ck(lib().g2v_topk_rows_bf16(_p(logits), rows, n, _rowmajor(logits), k, _p(out_idx), _p(out_val), _p(scratch),
+                                 scratch.numel() * 4 if scratch is not None else 0, _stream()), "g2v_topk_rows_bf16")
+    return out_idx, out_val
 
 
 def mrope_table_into(pos_i32, inv_freq, cos, sin):

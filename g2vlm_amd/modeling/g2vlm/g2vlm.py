@@ -15,7 +15,7 @@ import os
 import torch
 
 from ... import hip, host
-from ...engine import Engine, pack_continuations
+from ...engine import Engine, pack_continuations, pack_questions
 from ...weights import Weights
 from .qwen2vl import NaiveCache
 
@@ -568,7 +568,7 @@ class G2VLM:
         return conts
 
     @torch.no_grad()
-    def score_continuations(self, past_key_values, start_inputs, continuations):
+    def score_continuations(self, past_key_values, start_inputs, continuations, top_k=0):
         """Log-probabilities of given continuations after a prefill.  past_key_values / start_inputs: exactly what
         generate_text would be given (the pair _chat_prefill returns).  continuations: 1..64 lists of token ids, each of at
         least one id and at most Engine.SCORE_MAX_ROWS ids in all (ValueError otherwise).  Continuation c is scored as
@@ -578,47 +578,148 @@ class G2VLM:
         int32 [n] (0: the token greedy decode would have picked) and `total`, the sum of logprobs as a Python float.
         The cache is unchanged on return (same length, same bits in its rows), so generate_text or another
         score_continuations can follow on it.  decode_weights and decode_kv have no effect here: scoring is a prefill, and
-        prefills stay bf16."""
+        prefills stay bf16.
+        top_k > 0 (at most 32): every dict also carries `top_ids` int32 [n, top_k], the top_k most likely tokens of every
+        position in greedy decode's order (column 0 is what it would have picked; a token of rank r < top_k sits in column r),
+        and `top_logprobs` fp32 [n, top_k], their log-probabilities.  `logprobs` and `ranks` do not depend on top_k."""
         conts = self._check_continuations(continuations, "score_continuations")
+        Engine._check_top_k(top_k, "score_continuations")
         gi = start_inputs
         assert gi["packed_start_tokens"].numel() == 1 and past_key_values.length == int(_cpu(gi["key_values_lens"]).sum())
         start, pos = int(_cpu(gi["packed_start_tokens"])[0]), int(_cpu(gi["packed_query_position_ids"])[0, 0])
         ids, poss, seg_lens, targets = pack_continuations(start, pos, conts)
-        lp, rank = self.engine.score_rows(past_key_values, past_key_values.length, self._dev_i32(torch.tensor(ids)),
-                                          self._dev_i32(torch.tensor(poss).expand(3, -1)), seg_lens, self._dev_i32(torch.tensor(targets)))
-        lp, rank = lp.cpu(), rank.cpu()                       # the one wait, after the pass
+        res = self.engine.score_rows(past_key_values, past_key_values.length, self._dev_i32(torch.tensor(ids)),
+                                     self._dev_i32(torch.tensor(poss).expand(3, -1)), seg_lens, self._dev_i32(torch.tensor(targets)),
+                                     top_k=top_k)
+        return self._score_dicts(res, seg_lens)
+
+    @staticmethod
+    def _score_dicts(res, seg_lens):
+        """The device results of one scoring pass as one dict per segment (the one wait, after the pass)."""
+        res = [t.cpu() for t in res]
+        lp, rank = res[:2]
+        if len(res) > 2:
+            lse, top_ids, top_vals = res[2:]
+            top_lp = top_vals - lse[:, None]                  # fp32, as logprobs: x[t] - logsumexp
         out, off = [], 0
         for n in seg_lens:
-            out.append(dict(logprobs=lp[off:off + n].clone(), ranks=rank[off:off + n].clone(), total=float(lp[off:off + n].double().sum())))
+            d = dict(logprobs=lp[off:off + n].clone(), ranks=rank[off:off + n].clone(), total=float(lp[off:off + n].double().sum()))
+            if len(res) > 2:
+                d.update(top_ids=top_ids[off:off + n].clone(), top_logprobs=top_lp[off:off + n].clone())
+            out.append(d)
             off += n
         return out
 
     @torch.no_grad()
-    def chat_with_recon_choices(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt, choices,
-                                append_eos=True, normalize=False):
-        """Multiple choice over one scene: prefill as chat_with_recon does, then score every string of `choices` as the
-        assistant's answer - tokenised with add_special_tokens=False, followed by eos_token_id when append_eos - in one pass
-        (score_continuations).  Returns (best_index, scores, details): scores[j] is choice j's total log-probability, divided
-        by its number of tokens when `normalize`; details[j] its score_continuations dict plus `ids`.  Ties go to the lower
-        index.  ValueError, before the prefill, for an empty list, more than 64 choices, or a choice that tokenises to nothing.
-        decode_weights and decode_kv have no effect here."""
+    def score_questions(self, past_key_values, questions, top_k=0):
+        """score_continuations for several questions about one scene, in one pass (Engine.score_questions).
+        past_key_values: the scene's cache - system prompt, geometry views, ViT images, no question; read, and left as it was
+        (same length, same bits).  questions[j] = (text_inputs, start_inputs, continuations): what prepare_prompts_pure_text and
+        prepare_start_tokens return for question j behind that cache - every question from the scene's own (lens, rope), as
+        _chat_question does it - and 1..64 lists of token ids.  1..64 questions, at most 1024 continuations and
+        Engine.SCORE_MAX_ROWS rows (question tokens included) in all; ValueError otherwise, before anything is launched.
+        Question j's rows see the scene and themselves, its continuations the scene, question j and themselves: what they see
+        when question j is prefilled behind the scene and scored alone.  Returns, per question, the list of dicts
+        score_continuations returns (top_k as there).  decode_weights and decode_kv have no effect here."""
+        questions = list(questions)
+        if not 1 <= len(questions) <= Engine.SCORE_MAX_QUESTIONS:
+            raise ValueError(f"score_questions: 1..{Engine.SCORE_MAX_QUESTIONS} questions, got {len(questions)}")
+        Engine._check_top_k(top_k, "score_questions")
+        conts = [self._check_continuations(q[2], f"score_questions: question {j}") for j, q in enumerate(questions)]
+        if sum(len(c) for c in conts) > Engine.SCORE_MAX_CHOICES:
+            raise ValueError(f"score_questions: {sum(len(c) for c in conts)} continuations in all, at most {Engine.SCORE_MAX_CHOICES}")
+        rows = sum(int(q[0]["packed_text_ids"].numel()) for q in questions) + sum(len(t) for c in conts for t in c)
+        if rows > Engine.SCORE_MAX_ROWS:
+            raise ValueError(f"score_questions: {rows} rows in all, one scoring pass takes at most {Engine.SCORE_MAX_ROWS}")
+        plen, packed = past_key_values.length, []
+        for (ti, gi, _), c in zip(questions, conts):
+            m = int(ti["packed_text_ids"].numel())
+            assert int(_cpu(ti["key_values_lens"]).sum()) == plen and int(_cpu(gi["key_values_lens"]).sum()) == plen + m, \
+                "every question is prepared behind the scene's cache itself"
+            assert gi["packed_start_tokens"].numel() == 1
+            packed.append((_cpu(ti["packed_text_ids"]).tolist(), _cpu(ti["packed_text_position_ids"])[0].tolist(),
+                           int(_cpu(gi["packed_start_tokens"])[0]), int(_cpu(gi["packed_query_position_ids"])[0, 0]), c))
+        ids, poss, layout, targets = pack_questions(packed)
+        res = self.engine.score_questions(past_key_values, plen, self._dev_i32(torch.tensor(ids)),
+                                          self._dev_i32(torch.tensor(poss).expand(3, -1)), layout, self._dev_i32(torch.tensor(targets)),
+                                          top_k=top_k)
+        flat = self._score_dicts(res, [n for _, segs in layout for n in segs])
+        out, off = [], 0
+        for _, segs in layout:
+            out.append(flat[off:off + len(segs)])
+            off += len(segs)
+        return out
+
+    def _choice_ids(self, tokenizer, new_token_ids, choices, append_eos, what):
+        """The strings of `choices` as continuations: tokenised with add_special_tokens=False, eos_token_id behind when
+        append_eos.  ValueError for an empty list, more than 64 choices or a choice that tokenises to nothing."""
         choices = list(choices)
         if not 1 <= len(choices) <= Engine.SCORE_MAX_SEGMENTS:
-            raise ValueError(f"chat_with_recon_choices: 1..{Engine.SCORE_MAX_SEGMENTS} choices, got {len(choices)}")
+            raise ValueError(f"{what}: 1..{Engine.SCORE_MAX_SEGMENTS} choices, got {len(choices)}")
         conts = []
         for j, text in enumerate(choices):
             ids = [int(t) for t in tokenizer.encode(text, add_special_tokens=False)]
             if not ids:
-                raise ValueError(f"chat_with_recon_choices: choice {j} ({text!r}) tokenises to nothing")
+                raise ValueError(f"{what}: choice {j} ({text!r}) tokenises to nothing")
             conts.append(ids + ([int(new_token_ids["eos_token_id"])] if append_eos else []))
-        conts = self._check_continuations(conts, "chat_with_recon_choices")
-        past, gi = self._chat_prefill(tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt)
-        details = self.score_continuations(past, gi, conts)
+        return self._check_continuations(conts, what)
+
+    @staticmethod
+    def _pick(details, conts, normalize):
         for d, c in zip(details, conts):
             d["ids"] = c
         scores = [d["total"] / len(c) if normalize else d["total"] for d, c in zip(details, conts)]
         best = max(range(len(scores)), key=lambda j: (scores[j], -j))
         return best, scores, details
+
+    @torch.no_grad()
+    def chat_with_recon_choices(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt, choices,
+                                append_eos=True, normalize=False, top_k=0):
+        """Multiple choice over one scene: prefill as chat_with_recon does, then score every string of `choices` as the
+        assistant's answer - tokenised with add_special_tokens=False, followed by eos_token_id when append_eos - in one pass
+        (score_continuations).  Returns (best_index, scores, details): scores[j] is choice j's total log-probability, divided
+        by its number of tokens when `normalize`; details[j] its score_continuations dict (top_k as there) plus `ids`.  Ties go
+        to the lower index.  ValueError, before the prefill, for an empty list, more than 64 choices, or a choice that tokenises
+        to nothing.  decode_weights and decode_kv have no effect here."""
+        conts = self._choice_ids(tokenizer, new_token_ids, choices, append_eos, "chat_with_recon_choices")
+        Engine._check_top_k(top_k, "chat_with_recon_choices")
+        past, gi = self._chat_prefill(tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompt)
+        return self._pick(self.score_continuations(past, gi, conts, top_k=top_k), conts, normalize)
+
+    @torch.no_grad()
+    def chat_with_recon_questions_choices(self, tokenizer, new_token_ids, image_transform, dino_image_transform, images, prompts,
+                                          choices, append_eos=True, normalize=False, top_k=0):
+        """chat_with_recon_choices for several questions about the same views: the scene (system prompt, geometry views, ViT
+        images) is prefilled once, then every question and all its choices go through ONE scoring pass (score_questions).
+        `choices`: one list of strings per prompt, or one list of strings used for every prompt.  Returns one (best_index,
+        scores, details) per prompt, each as chat_with_recon_choices returns it for that prompt.  1..64 prompts, 1..64 choices
+        each, at most 1024 choices and Engine.SCORE_MAX_ROWS tokens (prompts included) in all: ValueError, before the prefill."""
+        what = "chat_with_recon_questions_choices"
+        prompts = list(prompts)
+        if not 1 <= len(prompts) <= Engine.SCORE_MAX_QUESTIONS:
+            raise ValueError(f"{what}: 1..{Engine.SCORE_MAX_QUESTIONS} prompts, got {len(prompts)}")
+        choices = list(choices)
+        if choices and all(isinstance(c, str) for c in choices):
+            choices = [choices] * len(prompts)
+        if len(choices) != len(prompts):
+            raise ValueError(f"{what}: {len(prompts)} prompts, {len(choices)} lists of choices")
+        conts = [self._choice_ids(tokenizer, new_token_ids, c, append_eos, f"{what}: prompt {j}") for j, c in enumerate(choices)]
+        Engine._check_top_k(top_k, what)
+        if sum(len(c) for c in conts) > Engine.SCORE_MAX_CHOICES:
+            raise ValueError(f"{what}: {sum(len(c) for c in conts)} choices in all, at most {Engine.SCORE_MAX_CHOICES}")
+        texts = [list(tokenizer.encode(p + "<|im_end|>\n<|im_start|>assistant")) for p in prompts]
+        rows = sum(len(t) for t in texts) + sum(len(t) for c in conts for t in c)
+        if min(len(t) for t in texts) < 1 or rows > Engine.SCORE_MAX_ROWS:
+            raise ValueError(f"{what}: {rows} tokens in all (at most {Engine.SCORE_MAX_ROWS}), every prompt at least one")
+        past, newlens, new_rope = self._chat_geometry(tokenizer, new_token_ids, dino_image_transform, images)
+        past, newlens, new_rope = self._chat_vit(past, newlens, new_rope, new_token_ids, image_transform, images)
+        questions = []
+        for prompt, c in zip(prompts, conts):
+            ti, qlens, qrope = self.prepare_prompts_pure_text(newlens, new_rope, [prompt + "<|im_end|>\n<|im_start|>assistant"],
+                                                              tokenizer, new_token_ids)
+            questions.append((ti, self.prepare_start_tokens(qlens, qrope, tokenizer, new_token_ids), c))
+        details = self.score_questions(past, questions, top_k=top_k)
+        return [self._pick(d, c, normalize) for d, c in zip(details, conts)]
 
     # ---- batched decode: several scenes answered together (SURVEY 8f-3; the reference is batch 1, g2vlm.py:1006, 1137)
     @torch.no_grad()

@@ -375,6 +375,26 @@ int g2v_decode_attn_pg_kv8(const void* qkv, const void* q_norm_w, const void* k_
 int64_t g2v_logprob_rows_workspace(int rows, int n);
 int g2v_logprob_rows_bf16(const void* x, int rows, int n, int64_t ld, const void* targets, void* out_lp, void* out_lse,
                           void* out_rank, void* scratch, int64_t scratch_bytes, void* stream);
+
+/* ---- top-k per row of logits (csrc/topk.hip): what the model preferred at a scored position ---------------------------------
+ * The first k elements of every row of bf16 x[rows, ld >= n] in g2v_argmax_rows_bf16's total order: larger value first,
+ * -0 == +0, every NaN above +inf, equal values by ascending index.  1 <= k <= G2V_TOPK_MAX.
+ * out_idx int32 [rows, k]         : entry j is the index of the element with exactly j elements before it in that order, so
+ *                                   out_idx[r][0] is what g2v_argmax_rows_bf16 gives for row r (NaN rows included) and, on a
+ *                                   NaN-free row, out_idx[r][j] is the one target for which g2v_logprob_rows_bf16 reports rank j
+ * out_val fp32 [rows, k] or NULL  : the selected elements' own values, converted exactly (a NaN's bits and a zero's sign kept)
+ * Entries j >= n (k > n) are index -1 and value NaN.  Every index written is in [0, n) or -1; columns [n, ld) are never read.
+ * One pass over the row, 16-byte loads where the row's base allows them.  The answer is exact and unique: a row's results
+ * depend on its n elements and k only - not on rows, on its position, on the alignment of its base or on `scratch`.
+ * scratch: as g2v_logprob_rows_bf16's - NULL, or int32 words zeroed ONCE by the caller (the kernel resets its tickets),
+ * >= g2v_topk_rows_workspace(rows, n, k) bytes: with it, the rows of a launch too small to fill the chip are each dealt out to
+ * several workgroups, which leave sorted k-lists there for the last of them to merge (no workgroup waits for another); without
+ * it every row is one workgroup's.  The workspace size is 0 where no split would be made.  hipGraph-capturable.
+ * -22 before any launch: rows <= 0, n <= 0, ld < n, k < 1, k > G2V_TOPK_MAX, x or out_idx NULL.                             */
+#define G2V_TOPK_MAX 32
+int64_t g2v_topk_rows_workspace(int rows, int n, int k);
+int g2v_topk_rows_bf16(const void* x, int rows, int n, int64_t ld, int k, void* out_idx, void* out_val, void* scratch,
+                       int64_t scratch_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif
