@@ -3,7 +3,8 @@ csrc/decode_layer.hip (g2v_gemv_pg, g2v_decode_attn_pg), csrc/decode_batch.hip (
 csrc/decode_fp8.hip.
 
 A helper module (pytest does not collect it): test_decode_check_cpu.py tests the table and the checks without a GPU,
-test_decode_fp64_gpu.py applies them to the bf16 kernels and test_fp8_decode_gpu.py to the e4m3 ones.
+test_decode_fp64_gpu.py applies them to the bf16 kernels; test_fp8_decode_check_cpu.py and test_fp8_decode_gpu.py do the same
+with the e4m3 table (TABLE8) and kernels.
 
 GEMVs.  Every output is checked element by element with gemm_check.check_gemm, unchanged: TAU = 2^-16, ULP_BOUND[EPI_SWIGLU] =
 2.0, zero flags, no fraction allowance.  The persistent-grid kernels accumulate with v_dot2 over at most 18 chunk steps per lane,
@@ -131,30 +132,52 @@ def check_swiglu(got, gu):
     return chk
 
 
+def row_exponents(N):
+    """int [N]: the exponent of the e4m3 scale row n gets when Case draws per-row magnitudes: 16 consecutive values over the 16
+    rows of a gate or up group, rotated by 5 from one group to the next.  Row n differs from n + d for every d a kernel could
+    confuse it with: 1 (the pair partner, the next row), 16 (the gate/up partner), 2, 3, 4, 6, 8 and 12 (the same slot of the
+    next batch)."""
+    n = torch.arange(N)
+    return (n % 16 + 5 * (n // 16)) % 16 - 19
+
+
+def fp8_weight(form, N, K, seed, row_scales=False):
+    """(q uint8 [N, K], s fp32 [N], wd bf16 [N, K] = the dequantised matrix) on the CPU, as Case draws them.  row_scales: every
+    row is multiplied by the power of two that makes the quantiser's scale of row n exactly 2^row_exponents(N)[n] (a power of
+    two commutes with the bf16 rounding and with the quantiser), instead of the random row factors of the 'lm' form."""
+    from g2vlm_amd.quant import dequantize_rows, quantize_rows_e4m3
+    w = rnd(N, K, seed=seed, scale=K ** -0.5)
+    if form == "gu":
+        w = interleave_gate_up(w[:N // 2].contiguous(), w[N // 2:].contiguous())
+    if row_scales:
+        _, s0 = quantize_rows_e4m3(w.bfloat16())
+        w = w * (torch.ldexp(torch.ones(N), row_exponents(N)) / s0).unsqueeze(1)
+    elif form == "lm":
+        w = w * torch.exp(2.0 * rnd(N, seed=seed + 5)).unsqueeze(1)                      # heavy-tailed row scales (synth.peaked_lm_head)
+    q, s = quantize_rows_e4m3(w.bfloat16())
+    return q, s, dequantize_rows(q, s)
+
+
 class Case:
     """Operands of one form.  form: 'qkv' (fp32 residual row, RMSNorm, bias, bf16 out), 'o' / 'down' (bf16 x, fp32 residual
     add), 'gu' (RMSNorm, interleaved gate/up rows, SwiGLU), 'lm' (RMSNorm, bf16 out), 'bias' (bf16 x, bias, bf16 out), 'sw'
     (first generation only: x = the gate/up vector bf16 [2K], SwiGLU applied on the fly, fp32 residual add).
-    quant: the weight goes through the e4m3 row quantiser (q, s; wd = the dequantised matrix); else wd = the bf16 matrix."""
+    quant: the weight goes through the e4m3 row quantiser (q, s; wd = the dequantised matrix); else wd = the bf16 matrix.
+    row_scales (quant only): per-row magnitudes, so that no row shares its scale with a neighbour (fp8_weight)."""
 
-    def __init__(self, form, B, N, K, seed, quant=True):
+    def __init__(self, form, B, N, K, seed, quant=True, row_scales=False):
         self.form, self.B, self.N, self.K = form, B, N, K
         self.norm = form in NORM_FORMS
         self.act = form == "gu"
         if quant:
-            from g2vlm_amd.quant import dequantize_rows, quantize_rows_e4m3
-            w = rnd(N, K, seed=seed, scale=K ** -0.5)
+            self.q, self.s, self.wd = (dev(t) for t in fp8_weight(form, N, K, seed, row_scales))
         else:                                                    # the bf16 matrices are drawn on the device (a C3 lm_head is 233 M values)
             g = torch.Generator(device="cuda"); g.manual_seed(seed)
             w = torch.randn((N, K), generator=g, device="cuda") * K ** -0.5
-        if form == "gu":
-            w = interleave_gate_up(w[:N // 2].contiguous(), w[N // 2:].contiguous())
-        if form == "lm":
-            w = w * torch.exp(2.0 * rnd(N, seed=seed + 5)).unsqueeze(1).to(w.device)     # heavy-tailed row scales (synth.peaked_lm_head)
-        if quant:
-            q, s = quantize_rows_e4m3(w.bfloat16())
-            self.q, self.s, self.wd = dev(q), dev(s), dev(dequantize_rows(q, s))
-        else:
+            if form == "gu":
+                w = interleave_gate_up(w[:N // 2].contiguous(), w[N // 2:].contiguous())
+            if form == "lm":
+                w = w * torch.exp(2.0 * rnd(N, seed=seed + 5)).unsqueeze(1).to(w.device)  # heavy-tailed row scales (synth.peaked_lm_head)
             self.q = self.s = None
             self.wd = w.bfloat16()
         self.bias = dev(rnd(N, seed=seed + 1, scale=0.1).bfloat16()) if form in ("qkv", "bias") else None
@@ -316,6 +339,96 @@ ROUTES = dict(zip([r for r in TABLE if r[0] in ("pg", "pgb")], (
     (1, 192, 1, 3), (1, 192, 1, 3), (2, 512, 1, 3), (2, 512, 1, 3), (2, 512, 1, 3), (1, 192, 1, 3), (1, 192, 1, 3),
     (1, 192, 1, 3), (2, 512, 1, 3), (2, 512, 1, 3), (2, 512, 1, 3),)))
 assert len(ROUTES) == sum(r[0] in ("pg", "pgb") for r in TABLE)
+
+
+# ------------------------------------------------------------------------------------------------ the e4m3 launch table
+# The same for the e4m3 entries ('pg8', 'pgb8'), whose plan is not the bf16 one: depths 1, 2, 3, 4, 6, 8, 12 (SwiGLU 1, 2, 3, 4, 6;
+# K > 2048: 1, 2), a batched unit is a pair of rows at depths 1, 2, 4 (NB = 8: 1, 2), the long-K batched kernel has S = ceil(K /
+# 1024) waves per block and R = 8 rows per pass (NB = 8: 4).  The five production shapes are tests/test_fp8_decode_gpu.py's REAL
+# and are not repeated.  Every Case of these rows is drawn with row_scales.  test_fp8_decode_check_cpu.py confirms the coverage.
+def _table8():
+    t = []
+    # batch 1, plain, K = 256 (192 threads): depths 1, 2, 3, 4, 6, 8, 12 in one trip; 8 + 1 and 12 + 1 ragged; 8 + 8 and 12 + 12
+    t += [("pg8", f, 8, N, 256) for f, N in (("bias", 1), ("o", 1281), ("lm", 2049), ("bias", 2561), ("o", 3585), ("qkv", 5121),
+                                             ("bias", 6401), ("qkv", 9217), ("o", 12801), ("lm", 11521), ("bias", 17921))]
+    # the other block sizes: 256, 320, 448, 512 threads at K = 256, 384 and 512 at a streaming K = 1536
+    t += [("pg8", f, 8, N, 256) for f, N in (("o", 769), ("bias", 1025), ("qkv", 1537), ("o", 16129))]
+    t += [("pg8", "qkv", 8, 8961, 1536), ("pg8", "o", 8, 8192, 1536)]
+    # batch 1, act (N = 2F, N % 32 == 0): depths 1, 2, 3, 4, 6 in one trip; 4 + 1 and 6 + 1 ragged; 4 + 4 and 6 + 6
+    t += [("pg8", "gu", 8, N, 256) for N in (32, 2592, 4128, 5152, 7200, 10272, 12832, 10784, 17952)]
+    t += [("pg8", "gu", 8, N, 1536) for N in (8224, 8192)]
+    # batch 1, long K (> 2048): depth 1, depth 2 in one trip, 2 + 1, 2 + 2 (at K >= 8960 the even trips start at N = 4609,
+    # a weight of 41 M elements: they run at K = 2064), 384 threads
+    t += [("pg8", f, 8, N, 2064) for f, N in (("bias", 1), ("o", 1281), ("down", 2049), ("bias", 2561), ("o", 300))]
+    t += [("pg8", f, 8, N, 8960) for f, N in (("down", 1), ("o", 1281), ("bias", 2049))]
+    t += [("pg8", f, 8, N, 9216) for f, N in (("bias", 1), ("down", 1281), ("o", 2049), ("bias", 1366))]
+    # batch 1, the other K: 16 (the smallest), 512 and 1024 (the last chunk step exactly full / wholly dead), 528 and 1040 (lane 0
+    # alone is live in the last step), 1536; 1552 and 2048 are short in e4m3 (two chunk steps, the second partly dead), plain only
+    for K in (16, 256, 512, 528, 1024, 1040, 1536):
+        t += [("pg8", "qkv", 8, 300, K), ("pg8", "o", 8, 7, K), ("pg8", "gu", 8, 96, K), ("pg8", "bias", 8, 301, K)]
+    for K in (1552, 2048):
+        t += [("pg8", "o", 8, 300, K), ("pg8", "bias", 8, 7, K), ("pg8", "down", 8, 1281, K)]
+    # batched, K <= 1536, units = pairs of rows; every N odd (the last unit has no second row), with a bf16 and a fused-norm
+    # activation.  NB = 2 (B = 1, 2) and NB = 4 (B = 3, 4): depths 1, 2, 4 in one trip, 4 + 1, 4 + 4; NB = 8 (B = 5 .. 8): depths
+    # 1, 2, then 2 + 1 and 2 + 2
+    plain = ((1, 1), (2, 4097), (1, 8193), (2, 16385), (1, 28673),
+             (3, 1), (4, 4097), (3, 8193), (4, 16385), (3, 28673),
+             (5, 1), (6, 4097), (7, 8193), (8, 12289))
+    for i, (B, N) in enumerate(plain):
+        t += [("pgb8", ("o", "bias")[i % 2], B, N, 256), ("pgb8", ("qkv", "lm")[i % 2], B, N, 256)]
+    # the pair without a second row as the last unit of a wave in a full batch (4 of 4, 2 of 2) and in a ragged last batch (4 + 1,
+    # 2 + 1); above it is the only unit of its wave (N = 1, 4097) or part of a short single batch
+    t += [("pgb8", "bias", 2, 16383, 256), ("pgb8", "o", 4, 20479, 256), ("pgb8", "qkv", 8, 8191, 256), ("pgb8", "o", 7, 12287, 256),
+          ("pgb8", "lm", 3, 8191, 256)]
+    # batched act: the same depths and trips
+    t += [("pgb8", "gu", B, N, 256) for B, N in ((1, 32), (2, 4128), (1, 8224), (2, 16416), (1, 28704),
+                                                  (3, 32), (4, 4128), (3, 8224), (4, 16416), (3, 28704),
+                                                  (5, 32), (6, 4128), (7, 8224), (8, 12320))]
+    # batched, the other K: slot 1 (chunks 64 ..) is empty up to K = 1024, holds one live lane per half-wave at 1040, all at 1536
+    for i, K in enumerate((16, 512, 528, 1024, 1040, 1536)):
+        t += [("pgb8", "qkv", 1 + i, 301, K), ("pgb8", "o", 8 - i, 7, K), ("pgb8", "gu", 2 + i, 96, K)]
+    # batched, long K (form 3): S = 2, 3, 6 (375 chunks in 384 slots), 9 (560 in 576), 9 (exact), 12 waves; R = 8 rows per pass
+    # at NB = 2, 4 and R = 4 at NB = 8; a block owns per = 1 row (blocks past N idle), R rows, R + 1 / R + 3 rows (ragged)
+    eps = ("bias", "o", "down")
+    for i, K in enumerate((1552, 2064, 6000, 8960, 9216, 12288)):
+        for j, N in enumerate((7, 2000, 2100)):
+            t.append(("pgb8", eps[(i + j) % 3], 1 + (i + j) % 4, N, K))
+        for j, N in enumerate((7, 1000, 1600)):
+            t.append(("pgb8", eps[(i + j + 1) % 3], 5 + (i + j) % 4, N, K))
+    assert len(set(t)) == len(t)
+    return t
+
+
+TABLE8 = _table8()
+# What g2v_gemv_pg_route(..., fp8 = true) answered for the rows of TABLE8, in order, when the table was written: (form, threads
+# per block, RB - form 3: the kernel's R -, KCH - form 3: the waves per block S).  Asserted before every launch.
+ROUTES8 = dict(zip(TABLE8, (
+    (1, 192, 1, 2), (1, 192, 2, 2), (1, 192, 3, 2), (1, 192, 4, 2), (1, 192, 6, 2), (1, 192, 8, 2), (1, 192, 12, 2),
+    (1, 192, 8, 2), (1, 192, 12, 2), (1, 192, 8, 2), (1, 192, 12, 2), (1, 256, 1, 2), (1, 320, 1, 2), (1, 448, 1, 2),
+    (1, 512, 8, 2), (1, 384, 6, 2), (1, 512, 4, 2), (1, 192, 1, 2), (1, 192, 2, 2), (1, 192, 3, 2), (1, 192, 4, 2),
+    (1, 192, 6, 2), (1, 192, 4, 2), (1, 192, 6, 2), (1, 192, 4, 2), (1, 192, 6, 2), (1, 384, 3, 2), (1, 512, 2, 2),
+    (1, 192, 1, 9), (1, 192, 2, 9), (1, 192, 2, 9), (1, 192, 2, 9), (1, 192, 1, 9), (1, 192, 1, 9), (1, 192, 2, 9),
+    (1, 192, 2, 9), (1, 192, 1, 9), (1, 192, 2, 9), (1, 192, 2, 9), (1, 384, 1, 9), (1, 192, 1, 2), (1, 192, 1, 2),
+    (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2),
+    (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2),
+    (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2),
+    (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 1, 2),
+    (1, 192, 2, 2), (1, 192, 1, 2), (1, 192, 1, 2), (1, 192, 2, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 2, 2),
+    (2, 512, 2, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2),
+    (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2),
+    (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 2, 2), (2, 512, 2, 2),
+    (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 2, 2),
+    (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 1, 2), (2, 512, 2, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2),
+    (2, 512, 1, 2), (2, 512, 2, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 4, 2), (2, 512, 1, 2), (2, 512, 2, 2),
+    (2, 512, 2, 2), (2, 512, 2, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2),
+    (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2),
+    (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (2, 512, 1, 2), (3, 128, 8, 2),
+    (3, 128, 8, 2), (3, 128, 8, 2), (3, 128, 4, 2), (3, 128, 4, 2), (3, 128, 4, 2), (3, 192, 8, 3), (3, 192, 8, 3),
+    (3, 192, 8, 3), (3, 192, 4, 3), (3, 192, 4, 3), (3, 192, 4, 3), (3, 384, 8, 6), (3, 384, 8, 6), (3, 384, 8, 6),
+    (3, 384, 4, 6), (3, 384, 4, 6), (3, 384, 4, 6), (3, 576, 8, 9), (3, 576, 8, 9), (3, 576, 8, 9), (3, 576, 4, 9),
+    (3, 576, 4, 9), (3, 576, 4, 9), (3, 576, 8, 9), (3, 576, 8, 9), (3, 576, 8, 9), (3, 576, 4, 9), (3, 576, 4, 9),
+    (3, 576, 4, 9), (3, 768, 8, 12), (3, 768, 8, 12), (3, 768, 8, 12), (3, 768, 4, 12), (3, 768, 4, 12), (3, 768, 4, 12),)))
+assert len(ROUTES8) == len(TABLE8)
 
 
 def case_id(row):
