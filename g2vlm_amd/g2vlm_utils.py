@@ -167,3 +167,82 @@ def save_ply_visualization(pred_dict, save_path, init_conf_threshold=20.0, filte
         ok = ~(np.isnan(p).any(1) | np.isinf(p).any(1))
         p, c = p[ok], c[ok]
     host.write_ply_binary(save_path, p, c)
+
+
+# ---- filtered export and intrinsics on the device (csrc/cloud.hip) -----------------------------------------------------------
+def _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images):
+    """Batch entry 0 of a recon result as the contiguous fp32 device tensors the kernels take, after every check that can
+    refuse the call: (points [N,H,W,3], local [N,H,W,3], conf [N,H,W] or None, images [N,3,H,W] or None, logit threshold)."""
+    logit = None
+    if conf_threshold is not None:
+        if pred_dict.get("conf") is None:
+            raise ValueError("conf_threshold needs pred_dict['conf']: this checkpoint has no confidence head (train_conf_pi3)")
+        logit = host.conf_logit_threshold(conf_threshold)
+    for name, tol in (("edge_rtol", edge_rtol), ("edge_atol", edge_atol)):
+        if tol is not None and not float(tol) >= 0.0:
+            raise ValueError(f"{name} must be >= 0, got {tol}")
+    points, local = pred_dict["points"], pred_dict["local_points"]
+    if points.dim() != 5 or points.shape[0] != 1 or points.shape[-1] != 3 or local.shape != points.shape:
+        raise ValueError(f"points / local_points [1,N,H,W,3] expected, got {tuple(points.shape)} / {tuple(local.shape)}")
+    n, h, w = points.shape[1:4]
+    images = pred_dict["images"] if need_images else pred_dict.get("images")
+    if images is not None:
+        if images.dim() != 5 or images.shape[0] != 1 or tuple(images.shape[1:3]) != (n, 3) or tuple(images.shape[3:]) != (h, w):
+            raise ValueError(f"images {tuple(images.shape)} do not match points {tuple(points.shape)}: [1,N,3,H,W] with the points' "
+                             "N, H, W expected (save_ply_visualization resamples; this export does not)")
+        images = images[0].detach().float().contiguous() if need_images else None
+    conf = None
+    if logit is not None:
+        conf = pred_dict["conf"]
+        if conf.numel() != n * h * w:
+            raise ValueError(f"conf {tuple(conf.shape)} does not match points {tuple(points.shape)}")
+        conf = conf.detach().float().reshape(n, h, w).contiguous()
+    return points[0].detach().float().contiguous(), local[0].detach().float().contiguous(), conf, images, logit
+
+
+def point_cloud_mask(pred_dict, conf_threshold=None, edge_rtol=None, edge_atol=None, filter_nan=True):
+    """Which pixels of a recon result belong in the cloud: bool [N,H,W] on the device (hip.cloud_mask).
+    filter_nan: the world point is finite.  conf_threshold: a probability p in (0,1); keeps sigmoid(conf) > p, evaluated as
+    conf > log(p/(1-p)).  edge_rtol / edge_atol: drops depth discontinuities ("flying pixels") by the reference's depth_edge
+    rule on the local depth (modeling/pi3/utils/geometry.py:339, 3x3 window)."""
+    from . import hip
+    points, local, conf, _, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=False)
+    if not (filter_nan or conf is not None or edge_rtol is not None or edge_atol is not None):
+        return torch.ones(points.shape[:3], dtype=torch.bool, device=points.device)
+    return hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan).view(torch.bool)
+
+
+def save_point_cloud(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_atol=None, filter_nan=True, verbose=True):
+    """save_ply_visualization's PLY with the filters of point_cloud_mask, packed on the device: mask, stable compaction into
+    15-byte records, ONE device-to-host copy of the kept records, one write.  With every filter but filter_nan off the file is
+    byte-identical to save_ply_visualization's.  Returns dict(num_points, counts = kept pixels per view)."""
+    from . import hip
+    points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=True)
+    if filter_nan or conf is not None or edge_rtol is not None or edge_atol is not None:
+        mask = hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan)
+    else:
+        mask = torch.ones(points.shape[:3], dtype=torch.uint8, device=points.device)
+    records, counts = hip.cloud_compact(points, images, mask)
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    host.write_ply_records(save_path, records.cpu())
+    counts = counts.cpu().tolist()
+    if verbose:
+        print(f"{save_path}: {records.shape[0]} of {mask.numel()} points kept, per view {counts}")
+    return dict(num_points=int(records.shape[0]), counts=counts)
+
+
+def estimate_intrinsics(pred_dict, mask=None):
+    """Pinhole intrinsics of every view from its local points (x z, y z, z) (reference g2vlm.py:1203-1205): the least-squares
+    fit u = fx X/Z + cx, v = fy Y/Z + cy over pixel centres, on the device (hip.intrinsics_lsq).  mask: bool / uint8 [N,H,W]
+    (point_cloud_mask's) restricts the fit.  Returns fp32 [1,N,3,3]; NaN where a view does not determine an entry."""
+    from . import hip
+    _, local, _, _, _ = _cloud_inputs(pred_dict, None, None, None, need_images=False)
+    if mask is not None:
+        mask = mask.to(local.device)
+        if mask.dim() == 4 and mask.shape[0] == 1:
+            mask = mask[0]
+        if tuple(mask.shape) != tuple(local.shape[:3]) or mask.dtype not in (torch.bool, torch.uint8):
+            raise ValueError(f"mask: bool [N,H,W] = {tuple(local.shape[:3])} expected, got {mask.dtype} {tuple(mask.shape)}")
+        mask = mask.contiguous()
+    K, _ = hip.intrinsics_lsq(local, mask)
+    return K.unsqueeze(0)

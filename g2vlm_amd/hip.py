@@ -103,6 +103,11 @@ _SIGS = {
     "g2v_logprob_rows_bf16": ([_P, _I, _I, _L, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_topk_rows_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_topk_rows_bf16": ([_P, _I, _I, _L, _I, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_mask": ([_P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _P, _P], C.c_int),
+    "g2v_cloud_compact_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_cloud_compact": ([_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P], C.c_int),
+    "g2v_intrinsics_lsq_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_intrinsics_lsq": ([_P, _P, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -919,6 +924,103 @@ def topk_rows_bf16(logits, k, out_idx=None, out_val=None, scratch=None):
     _ck(lib().g2v_topk_rows_bf16(_p(logits), rows, n, _rowmajor(logits), k, _p(out_idx), _p(out_val), _p(scratch),
                                  scratch.numel() * 4 if scratch is not None else 0, _stream()), "g2v_topk_rows_bf16")
     return out_idx, out_val
+
+
+# ------------------------------------------------------------------------------------------ point-cloud export (csrc/cloud.hip)
+CLOUD_FINITE, CLOUD_CONF, CLOUD_EDGE_ATOL, CLOUD_EDGE_RTOL = 1, 2, 4, 8       # G2V_CLOUD_*
+_cloud_ws = {}
+
+
+def _cloud_workspace(nbytes, device, tag):
+    """Scratch of the compaction's block counts / the fit's partial sums: one per scratch_owner and use, grown when a launch
+    needs more (it carries nothing from one call to the next and needs no zeroing)."""
+    key = scratch_owner(device.index) + (tag,)
+    ws = _cloud_ws.get(key)
+    if ws is None or ws.numel() * 8 < nbytes:
+        ws = _cloud_ws[key] = torch.empty(max((nbytes + 7) // 8, 1), dtype=torch.int64, device=device)
+    return ws
+
+
+def _nhw3(t, what):
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[3] == 3 and t.is_contiguous(), f"{what}: fp32 [N,H,W,3], contiguous"
+    return tuple(t.shape[:3])
+
+
+def cloud_mask(points=None, local=None, conf=None, conf_logit_min=0.0, edge_atol=None, edge_rtol=None, finite=True, out=None):
+    """Keep mask uint8 [N,H,W] of recon's pointmaps (g2v_cloud_mask): 1 where every enabled test passes.
+    finite: the three coordinates of points fp32 [N,H,W,3] are finite.  conf fp32 [N,H,W] given: conf > conf_logit_min as an
+    fp32 compare (logits; NaN fails).  edge_atol / edge_rtol given: not an edge of local[..., 2] under the reference's
+    depth_edge rule (3x3 window; local fp32 [N,H,W,3])."""
+    flags = (CLOUD_FINITE if finite else 0) | (CLOUD_CONF if conf is not None else 0) | \
+        (CLOUD_EDGE_ATOL if edge_atol is not None else 0) | (CLOUD_EDGE_RTOL if edge_rtol is not None else 0)
+    edge = flags & (CLOUD_EDGE_ATOL | CLOUD_EDGE_RTOL)
+    shapes = []
+    if finite:
+        shapes.append(_nhw3(points, "points"))
+    if edge:
+        shapes.append(_nhw3(local, "local"))
+    if conf is not None:
+        assert conf.is_cuda and conf.dtype == torch.float32 and conf.dim() == 3 and conf.is_contiguous(), "conf: fp32 [N,H,W], contiguous"
+        shapes.append(tuple(conf.shape))
+    assert shapes, "cloud_mask: no test enabled and no input to take the shape from"
+    assert all(s == shapes[0] for s in shapes), f"cloud_mask: inputs disagree on [N,H,W]: {shapes}"
+    N, H, W = shapes[0]
+    dev = (points if finite else local if edge else conf).device
+    if out is None:
+        out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    assert out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (N, H, W) and out.is_contiguous()
+    _ck(lib().g2v_cloud_mask(_p(points) if finite else None, _p(local) if edge else None, _p(conf), N, H, W, flags, float(conf_logit_min),
+                             float(edge_atol or 0.0), float(edge_rtol or 0.0), _p(out), _stream()), "g2v_cloud_mask")
+    return out
+
+
+def cloud_compact_workspace(N, H, W):
+    return int(lib().g2v_cloud_compact_workspace(int(N), int(H), int(W)))
+
+
+def cloud_compact(points, colors, mask, workspace=None):
+    """The pixels mask keeps as packed PLY records (g2v_cloud_compact): points fp32 [N,H,W,3], colors fp32 [N,3,H,W] in [0,1],
+    mask uint8 or bool [N,H,W] -> (records uint8 [M,15] = <f4 x,y,z + u1 r,g,b in view-major, row-major order, counts int32
+    [N]).  Synchronous: the total M is read back once to size the result (a view of a buffer of N*H*W records)."""
+    N, H, W = _nhw3(points, "points")
+    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
+        "colors: fp32 [N,3,H,W], contiguous"
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    nbytes = cloud_compact_workspace(N, H, W)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, points.device, "compact")
+    cap = N * H * W
+    records = torch.empty((cap, 15), dtype=torch.uint8, device=points.device)
+    counts = torch.empty(N, dtype=torch.int32, device=points.device)
+    _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(mask), N, H, W, _p(records), cap, _p(counts), _p(workspace),
+                                workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_compact")
+    m = int(counts.sum(dtype=torch.int64).item())
+    return records[:m], counts
+
+
+def intrinsics_lsq_workspace(N, H, W):
+    return int(lib().g2v_intrinsics_lsq_workspace(int(N), int(H), int(W)))
+
+
+def intrinsics_lsq(local, mask=None, workspace=None):
+    """Per view the least-squares pinhole matrix of local points fp32 [N,H,W,3] (g2v_intrinsics_lsq): u = fx X/Z + cx,
+    v = fy Y/Z + cy over pixel centres (x + 0.5, y + 0.5) and the pixels mask keeps (None: all) with finite X, Y, Z and Z > 0.
+    Returns (K fp32 [N,3,3], used int32 [N]); entries that the pixels do not determine are NaN.  Bit-reproducible."""
+    N, H, W = _nhw3(local, "local")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    nbytes = intrinsics_lsq_workspace(N, H, W)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, local.device, "intrinsics")
+    K = torch.empty((N, 3, 3), dtype=torch.float32, device=local.device)
+    used = torch.empty(N, dtype=torch.int32, device=local.device)
+    _ck(lib().g2v_intrinsics_lsq(_p(local), _p(mask), N, H, W, _p(K), _p(used), _p(workspace),
+                                 workspace.numel() * workspace.element_size(), _stream()), "g2v_intrinsics_lsq")
+    return K, used
 
 
 def mrope_table_into(pos_i32, inv_freq, cos, sin):

@@ -344,3 +344,26 @@ def write_ply_binary(path, points, colors01):
     with open(path, "wb") as f:
         f.write(hdr.encode("ascii"))
         f.write(rec.tobytes())
+
+
+def write_ply_records(path, records_u8):
+    """write_ply_binary for records that are packed already: uint8 [M, 15] (numpy or a host tensor), each <f4 x, y, z +
+    u1 r, g, b as hip.cloud_compact leaves them.  Same header text, so the same file for the same points."""
+    rec = records_u8.numpy() if torch.is_tensor(records_u8) else np.asarray(records_u8)
+    if rec.dtype != np.uint8 or rec.ndim != 2 or rec.shape[1] != 15:
+        raise ValueError(f"write_ply_records: uint8 [M, 15] expected, got {rec.dtype} {rec.shape}")
+    hdr = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {rec.shape[0]}\n"
+           "property float x\nproperty float y\nproperty float z\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(np.ascontiguousarray(rec).tobytes())
+
+
+def conf_logit_threshold(p):
+    """The confidence threshold of the point-cloud filters as the logit the device compares with: log(p / (1 - p)) in fp64,
+    rounded to fp32 once, so that `conf > threshold` on the logits is an exact statement.  p is a probability in (0, 1)."""
+    p = float(p)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"conf_threshold is a probability in (0, 1), got {p}")
+    return float(np.float32(math.log(p / (1.0 - p))))

@@ -395,6 +395,46 @@ int g2v_logprob_rows_bf16(const void* x, int rows, int n, int64_t ld, const void
 int64_t g2v_topk_rows_workspace(int rows, int n, int k);
 int g2v_topk_rows_bf16(const void* x, int rows, int n, int64_t ld, int k, void* out_idx, void* out_val, void* scratch,
                        int64_t scratch_bytes, void* stream);
+
+/* ---- point-cloud export (csrc/cloud.hip): what follows `recon` ------------------------------------------------------------
+ * Inputs are recon's outputs for one batch entry: points / local fp32 [N,H,W,3], conf fp32 [N,H,W] (logits), colors fp32
+ * [N,3,H,W] (the `images` layout).  Every entry point returns -22 before any launch on a NULL pointer its flags require, on
+ * N, H or W <= 0, on N*H*W > 2^31 - 1 (and N or ceil(H/16) > 65535), on a pointer that is not 4-byte aligned, and on a workspace
+ * that is missing or smaller than its query says.  Workspaces need no initialisation.  hipGraph-capturable.
+ *
+ * g2v_cloud_mask: mask u8 [N,H,W] = 1 where every test enabled in `flags` passes.
+ *   G2V_CLOUD_FINITE     the three coordinates of `points` are finite
+ *   G2V_CLOUD_CONF       conf > conf_logit_min, an fp32 compare (the caller turns a probability p into log(p / (1 - p)) in
+ *                        fp64, rounded to fp32 once; no sigmoid is evaluated here); a NaN logit fails
+ *   G2V_CLOUD_EDGE_ATOL, G2V_CLOUD_EDGE_RTOL   the pixel is dropped if it is an edge of d = local[..., 2] under the
+ *                        reference's depth_edge (modeling/pi3/utils/geometry.py:339; 3x3 window, no mask): over the in-bounds
+ *                        pixels of the window (never across a row, column or view boundary), a NaN among them means "not an edge";
+ *                        else diff = max(window) + max(-window) in fp32; an edge if diff > atol (ATOL) or if q > rtol (RTOL)
+ *                        for q = diff / d_centre, correctly rounded, NaN -> 0, +-inf -> +-FLT_MAX
+ *   `points` may be NULL without FINITE, `conf` without CONF, `local` without either EDGE bit.
+ *
+ * g2v_cloud_compact: the kept pixels (mask != 0) as packed 15-byte PLY records (<f4 x, y, z; u1 r, g, b) in view-major,
+ *   row-major order - numpy boolean indexing's - into records u8 [max_records, 15]; counts int32 [N] receives the kept pixels
+ *   of every view (always their true number).  Records past max_records are not written (max_records = N*H*W always
+ *   suffices; 0 with records NULL only counts).  The colour byte is (uint8)(min(max((double)c, 0), 1) * 255), truncated;
+ *   colours are assumed finite.  Positions are integer prefix sums: the bytes are the same on every run.
+ *
+ * g2v_intrinsics_lsq: per view the least-squares pinhole fit u = fx X/Z + cx, v = fy Y/Z + cy over pixel centres
+ *   u = x + 0.5, v = y + 0.5 and the pixels of `local` that mask keeps (NULL: all) with finite X, Y, Z and Z > 0.  Ratios and
+ *   sums in fp64, reduced in a fixed order (no atomics): the same bits on every run.  K fp32 [N,3,3] = {fx 0 cx; 0 fy cy; 0 0 1},
+ *   used int32 [N] = pixels fitted.  Fewer than 2 such pixels, or no variance of X/Z (Y/Z), gives NaN for fx, cx (fy, cy).  */
+#define G2V_CLOUD_FINITE 1
+#define G2V_CLOUD_CONF 2
+#define G2V_CLOUD_EDGE_ATOL 4
+#define G2V_CLOUD_EDGE_RTOL 8
+int g2v_cloud_mask(const void* points, const void* local, const void* conf, int N, int H, int W, int flags, float conf_logit_min,
+                   float edge_atol, float edge_rtol, void* mask, void* stream);
+int64_t g2v_cloud_compact_workspace(int N, int H, int W);
+int g2v_cloud_compact(const void* points, const void* colors, const void* mask, int N, int H, int W, void* records,
+                      int64_t max_records, void* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t g2v_intrinsics_lsq_workspace(int N, int H, int W);
+int g2v_intrinsics_lsq(const void* local, const void* mask, int N, int H, int W, void* K, void* used, void* workspace,
+                       int64_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,9 @@
 """Drop-in counterpart of the reference's inference_recon.py (same flags), running on g2vlm_amd.
-Fixes the reference's Namespace-as-path bug and sorts the folder listing."""
+Fixes the reference's Namespace-as-path bug and sorts the folder listing.
+
+Flags of this project's own, all off by default (without them main() does what the reference's does): --conf-threshold,
+--edge-rtol, --edge-atol write the PLY through save_point_cloud's device filters; --intrinsics fits and prints a pinhole
+matrix per view."""
 import argparse
 import os
 import sys
@@ -11,6 +15,12 @@ parser = argparse.ArgumentParser(description="Demo for 3D visualization")
 parser.add_argument("--image_folder", type=str, default="examples/dl3dv/", help="Path to folder containing images")
 parser.add_argument("--model_path", type=str, default="InternRobotics/G2VLM-2B-MoT")
 parser.add_argument("--save_path", type=str, default="results/arkitscenes_results.ply")
+parser.add_argument("--conf-threshold", type=float, default=None, metavar="P",
+                    help="keep points whose confidence sigmoid(conf) exceeds P in (0,1); needs a checkpoint with a confidence head")
+parser.add_argument("--edge-rtol", type=float, default=None, metavar="R",
+                    help="drop depth discontinuities: 3x3 depth range / depth above R (0.03 is the usual choice)")
+parser.add_argument("--edge-atol", type=float, default=None, metavar="A", help="drop depth discontinuities: 3x3 depth range above A")
+parser.add_argument("--intrinsics", action="store_true", help="fit, print and return a pinhole matrix per view (pred['intrinsics'])")
 
 
 def main(argv=None):
@@ -20,7 +30,19 @@ def main(argv=None):
     print(image_names)
     model, tokenizer, new_token_ids, vit_image_transform, dino_transform = load_model_and_tokenizer(args.model_path)
     pred = model.recon(tokenizer, new_token_ids, dino_transform, image_names)
-    save_ply_visualization(pred, args.save_path)
+    filtered = args.conf_threshold is not None or args.edge_rtol is not None or args.edge_atol is not None
+    if filtered:
+        from g2vlm_utils import save_point_cloud
+        save_point_cloud(pred, args.save_path, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol)
+    else:
+        save_ply_visualization(pred, args.save_path)
+    if args.intrinsics:
+        from g2vlm_utils import estimate_intrinsics
+        # over every valid pixel: X/Z and Y/Z of a local point (xy z, z) do not depend on its depth, so the depth filters have
+        # nothing to remove from this fit
+        pred["intrinsics"] = estimate_intrinsics(pred)
+        for i, k in enumerate(pred["intrinsics"][0].cpu().tolist()):
+            print(f"view {i}: K = {k}")
     return pred
 
 
