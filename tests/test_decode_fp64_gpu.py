@@ -24,6 +24,25 @@ of their bound (first generation 0.024, gemv_pg_batch 0.020, gemv_pg 0: every va
 0.39 % multi-valued elements (MULTI_CAP 2 %); 18 - 58 % of the GEMV outputs have more than one admissible value.
 g2v_decode_attn_pg: rel at most 2.2e-3, worst element 1.2e-2 of the rms.  First generation: rel at most 1.1e-4 against the
 bf16-rounded fp64 attention, worst element 1.1e-2 of the rms; no launch of any kernel here was flagged, so csrc/ is unchanged.
+
+Structured score profiles (tests/attn_profile_check.py: families, plan mirror, the hard and the sharp bound with their
+derivation; tests/test_attn_profile_cpu.py: the bounds proven on an emulation of the core, the planted errors).  The cached
+rows are built from the q of the step, so that a head's scores follow a sawtooth per wave, rise or fall over the cache, hold one
+peak key, spread over +-120 log2 units, sit at +-250 or are all equal; g2v_decode_attn_pg at B = 32 / max_len 2176 (three
+batches per wave), B = 1 / 4160 (128 partials of one batch) and G = 8 at B = 3 / 17000, g2v_decode_attn_batch at B = 8 / 4160.
+Zero elements over either bound, the peak-200 cases bit-equal to the peak key's V row.  Measured maxima of |err| / hard bound
+and |err| / sharp bound on an MI355X, the CPU emulation's beside them:
+                 g2v_decode_attn_pg    emulation        g2v_decode_attn_batch (hard1 / sharp1)   its emulation
+  saw            0.75 / 0.38           0.81 / 0.42      0.97 / 0.97                               0.98 / 0.98
+  saw_even       0.75 / 0.38           0.81 / 0.45      -
+  rise           0.75 / 0.40           0.81 / 0.39      -
+  fall           0.75 / 0.41           0.81 / 0.38      -
+  peak           0.51 / 0.28           0.47 / 0.25      0.000 / 0.000                             0.001 / 0.001
+  wide           0.67 / 0.38           0.68 / 0.32      0.94 / 0.93                               0.96 / 0.95
+  offset         0.53 / 0.41           0.57 / 0.38      -
+  flat           0.75 / -              0.81 / -         -
+(0.75 / 0.81: the two-key slots, the same rows in every family.  The first generation keeps its weights in fp32: its bounds are
+the output's bf16 rounding plus an fp32 term, and a half-ulp rounding reaches them.)  No kernel was flagged: csrc/ is unchanged.
 """
 import os
 import sys
@@ -32,6 +51,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import attn_profile_check as P  # noqa: E402
 import decode_check as D  # noqa: E402
 import gemm_check as G  # noqa: E402
 import rowop_check as R  # noqa: E402
@@ -41,6 +61,7 @@ LENS = [1, 2, 32, 33, 65, 357, 4103]                         # cache lengths INC
 SLOTS = [(1, i) for i in range(7)] + [(3, 0), (3, 3), (3, 6), (8, 0)]
 MEASURED = {}
 WORST = {}
+PROFILE = P.Ratios()
 
 
 def worst(name, **kw):
@@ -57,6 +78,7 @@ def measured():
               f"swiglu {v['max_ulps']:.2f} ulp")
     for k, v in sorted(WORST.items()):
         print(f"[bf16 decode] {k}: " + " ".join(f"{a} {b:.3e}" for a, b in sorted(v.items())))
+    PROFILE.report("bf16 decode profiles")
     D._EYE.clear()
 
 
@@ -160,16 +182,20 @@ def slot_lengths(B, shift):
     return [LENS[(z + shift) % len(LENS)] for z in range(B)]
 
 
-def make_step(hip, lens, Hq, Hkv, seed, max_len=None, pad=192):
+def make_step(hip, lens, Hq, Hkv, seed, max_len=None, pad=192, edit=None):
     """One decode step over B = len(lens) slots in the engine's form: caches [B, scene_rows, Hkv, 128] with scene_rows = max_len
-    + pad, Gaussian bf16 rows [0, n - 1) per slot, NaN in the new row n - 1 and in every row behind it."""
+    + pad, Gaussian bf16 rows [0, n - 1) per slot, NaN in the new row n - 1 and in every row behind it.  edit: applied to the raw
+    qkv rows (on the host, in place) before anything is derived from them."""
     B = len(lens)
     if max_len is None:
         max_len = (max(lens) + 40 + 63) // 64 * 64
     assert max(lens) <= max_len
     rows = max_len + pad
     g = torch.Generator(); g.manual_seed(seed)
-    qkv = torch.randn((B, (Hq + 2 * Hkv) * 128), generator=g).bfloat16().cuda()
+    qkv = torch.randn((B, (Hq + 2 * Hkv) * 128), generator=g).bfloat16()
+    if edit is not None:
+        edit(qkv)
+    qkv = qkv.cuda()
     qw = (1 + 0.1 * torch.randn(128, generator=g)).cuda()
     kw = (1 + 0.1 * torch.randn(128, generator=g)).cuda()
     pos = torch.tensor([[n - 1 for n in lens]] * 3, dtype=torch.int32, device="cuda")
@@ -361,3 +387,67 @@ def test_first_generation_attentions_against_fp64_and_each_other(hip, Hq, B, shi
         r = assert_bf16_close(o_static, want.bfloat16(), ulps=1.01)
         _, e = D.row_metrics(o_static, want)
         worst("attn gen1", rel=r, elem=e)
+
+
+# ------------------------------------------------------------------------------------------------ structured score profiles
+def profile_step(hip, case, variant, lens, Hq, Hkv, seed, max_len, waves, kb=P.KB):
+    """make_step with the cached rows of every slot replaced by the builder's (tests/attn_profile_check.py), built from the q
+    that qknorm_mrope_cache leaves for the step's qkv; the rows at and behind the new one stay NaN."""
+    new = P.new_row_slots(case, lens, variant)
+    s = make_step(hip, lens, Hq, Hkv, seed, max_len, edit=lambda qkv: P.align_new_k(qkv, Hq, Hkv, new))
+    knew = torch.stack([s["k_ref"][z, n - 1] for z, n in enumerate(lens)]).cpu()
+    Ks, Vs, s["infos"] = P.build_step(case, s["qn"].cpu(), knew, lens, Hq, Hkv, waves, seed + 1, variant, kb=kb)
+    for z, n in enumerate(lens):
+        if n > 1:
+            for name, rows in (("kc", Ks[z]), ("k_ref", Ks[z]), ("vc", Vs[z]), ("v_ref", Vs[z])):
+                s[name][z, :n - 1] = rows.cuda()
+        assert torch.isnan(s["kc"][z, n - 1:].float()).all() and torch.isnan(s["vc"][z, n - 1:].float()).all()
+    return s
+
+
+def check_profile(name, case, s, out, Hq, Hkv, gen1=False):
+    """Every slot of out [B, Hq 128] against fp64 attention over the reference cache rows [0, n) under the hard and the sharp
+    bound, no element exempt; an exact case (peak 200) must equal the peak key's V row bit for bit."""
+    G_ = Hq // Hkv
+    qn, k, v, out = s["qn"].cpu(), s["k_ref"].cpu(), s["v_ref"].cpu(), out.cpu()
+    over = 0
+    for z, n in enumerate(s["lens"]):
+        o = out[z].view(Hq, 128)
+        over += P.check_slot(PROFILE, name, case[0], o, qn[z].view(Hq, 128), k[z, :n], v[z, :n], Hkv, gen1=gen1)
+        for h in range(Hkv):
+            if s["infos"][z][h]["exact"]:
+                assert torch.equal(bits(o[h * G_:(h + 1) * G_]), bits(v[z, s["infos"][z][h]["peak"], h].expand(G_, 128))), (z, h)
+    w = PROFILE.worst[name]
+    print(f"[{name}] |err| / hard {w['hard']:.3f}  |err| / sharp {w['sharp']:.3f}")
+    assert over == 0, (name, over, w)
+
+
+@pytest.mark.parametrize("shape,cv", [(sh, cv) for sh in ("b32", "b1", "g8") for cv in P.pg_cases(sh)],
+                         ids=lambda v: v if isinstance(v, str) else P.pg_case_id(v))
+def test_attn_pg_on_structured_score_profiles(hip, shape, cv):
+    """g2v_decode_attn_pg on every family of tests/attn_profile_check.py at the shapes P.PG_SHAPES: the appended rows bit for
+    bit, the rows below untouched, NaN behind, and the output inside both bounds."""
+    case, variant = cv
+    Hq, Hkv, max_len, lens = P.PG_SHAPES[shape]
+    waves = P.pg_waves(max_len, P.pg_nbh(Hkv, len(lens)))
+    s = profile_step(hip, case, variant, lens, Hq, Hkv, 50 + len(lens) + variant, max_len, waves)
+    out = run_pg(hip, s, Hq, Hkv)
+    torch.cuda.synchronize()
+    assert torch.equal(bits(s["kc"]), bits(s["k_ref"])) and torch.equal(bits(s["vc"]), bits(s["v_ref"]))
+    for z, n in enumerate(lens):
+        assert torch.isfinite(s["kc"][z, :n].float()).all() and torch.isnan(s["kc"][z, n:].float()).all(), z
+        assert torch.isnan(s["vc"][z, n:].float()).all(), z
+    check_profile(f"attn_pg {shape} {P.case_id(case)}", case, s, out, Hq, Hkv)
+
+
+@pytest.mark.parametrize("case", P.GEN1_CASES, ids=P.case_id)
+def test_first_generation_attention_on_structured_score_profiles(hip, case):
+    """g2v_decode_attn_batch (the other first-generation entries are bit-equal to it by the test above) on the sawtooth, the
+    peak and the wide family at B = 8, max_len = 4160, under the first generation's own two bounds (fp32 weights)."""
+    Hq, Hkv, max_len, lens = P.GEN1_SHAPE
+    s = profile_step(hip, case, 0, lens, Hq, Hkv, 70, max_len, P.gen1_waves(max_len), kb=16)
+    ws = torch.empty(len(lens) * hip.decode_attn_workspace(max_len, Hq) // 4, dtype=torch.float32, device="cuda")
+    out = D.nan_bf16(len(lens), Hq * 128)
+    hip.decode_attn_batch(s["qn"], s["k_ref"], s["v_ref"], out, s["ld"], s["rows"], max_len, Hq, Hkv, 128 ** -0.5, ws)
+    torch.cuda.synchronize()
+    check_profile(f"attn gen1 {P.case_id(case)}", case, s, out, Hq, Hkv, gen1=True)

@@ -2,7 +2,14 @@
 
 g2v_kv_quant_e4m3 / g2v_kv_dequant_e4m3 against the host quantiser (g2vlm_amd/quant.py), and g2v_decode_attn_pg_kv8 - one
 decode-attention step over an e4m3 cache that appends the new token's row quantised - against an fp64 softmax attention over the
-dequantised cache, against what qknorm_mrope_cache appends in bf16, and against g2v_decode_attn_pg on the unquantised rows."""
+dequantised cache, against what qknorm_mrope_cache appends in bf16, and against g2v_decode_attn_pg on the unquantised rows.
+
+Structured score profiles (tests/attn_profile_check.py, proven on the CPU by tests/test_attn_profile_cpu.py): the families
+through the host quantiser at B = 32 / 2176, B = 1 / 4160 and G = 8 at B = 3 / 17000; rise 20 and fall 20 put nine distinct K
+scales into one slot (at least six asserted).  Zero elements over the hard or the sharp bound, the peak-200 cases bit-equal to
+the peak key's dequantised V row.  Measured maxima of |err| / hard and |err| / sharp on an MI355X | the CPU emulation:
+  saw 0.75 / 0.40 | 0.68 / 0.39     saw_even 0.75 / 0.39 | 0.68 / 0.41     rise 0.75 / 0.40 | 0.68 / 0.39     fall 0.75 / 0.44 | 0.68 / 0.40
+  peak 0.46 / 0.23 | 0.47 / 0.26    wide 0.71 / 0.35 | 0.67 / 0.34         offset 0.48 / 0.36 | 0.48 / 0.34   flat 0.75 / - | 0.68 / -"""
 import os
 import sys
 
@@ -16,9 +23,17 @@ sys.path.insert(0, HERE)
 
 from g2vlm_amd.quant import dequantize_rows, quantize_rows_e4m3  # noqa: E402
 from test_kv8_cpu import attention64, magnitude_rows  # noqa: E402
+import attn_profile_check as P  # noqa: E402
 
 LENS = [1, 2, 32, 33, 65, 357, 4103]                         # cache lengths INCLUDING the new token, mixed over the slots
 POISON = 0x7F                                                # the e4m3fn NaN code
+PROFILE = P.Ratios()
+
+
+@pytest.fixture(scope="module", autouse=True)
+def measured():
+    yield
+    PROFILE.report("kv8 profiles")
 
 
 @pytest.fixture(scope="module")
@@ -90,13 +105,19 @@ def test_dequant_is_exact_for_every_code(hip):
 
 
 # ------------------------------------------------------------------------------------------------ the attention
-def make_step(hip, lens, Hq, Hkv, seed):
+def make_step(hip, lens, Hq, Hkv, seed, cap=None, edit=None):
     """One decode step over B = len(lens) slots.  The cache rows [0, n - 1) of slot z are Gaussian bf16 rows through the host
-    quantiser; the new row n - 1 and everything past it are poisoned: NaN codes, NaN scales."""
+    quantiser; the new row n - 1 and everything past it are poisoned: NaN codes, NaN scales.  cap: the capacity (default: the
+    64-row bucket above the longest slot); edit: applied to the raw qkv rows on the host, in place."""
     B = len(lens)
-    cap = (max(lens) + 40 + 63) // 64 * 64
+    if cap is None:
+        cap = (max(lens) + 40 + 63) // 64 * 64
+    assert max(lens) <= cap
     g = torch.Generator(); g.manual_seed(seed)
-    qkv = torch.randn((B, (Hq + 2 * Hkv) * 128), generator=g).bfloat16().cuda()
+    qkv = torch.randn((B, (Hq + 2 * Hkv) * 128), generator=g).bfloat16()
+    if edit is not None:
+        edit(qkv)
+    qkv = qkv.cuda()
     qw = (1 + 0.1 * torch.randn(128, generator=g)).cuda()
     kw = (1 + 0.1 * torch.randn(128, generator=g)).cuda()
     pos = torch.tensor([[n - 1 for n in lens]] * 3, dtype=torch.int32, device="cuda")
@@ -247,3 +268,71 @@ def test_kv8_attention_replays_from_a_graph_bit_identically(hip):
     for z, n in enumerate(lens):                             # the three new rows of every slot are written, poison beyond
         assert torch.isfinite(ce[2][z, :n + 2]).all() and torch.isnan(ce[2][z, n + 2:]).all(), z
         assert not (ce[0][z, n - 1:n + 2] == POISON).all(dim=-1).any() and (ce[0][z, n + 2:] == POISON).all(), z
+
+
+# ------------------------------------------------------------------------------------------------ structured score profiles
+def roundtrip(rows):
+    """bf16 rows as the e4m3 cache holds them."""
+    q, sc = host_quant(rows.reshape(-1, 1, 128))
+    return host_dequant(q, sc).view(rows.shape)
+
+
+@pytest.mark.parametrize("shape,cv", [(sh, cv) for sh in ("b32", "b1", "g8") for cv in P.pg_cases(sh)],
+                         ids=lambda v: v if isinstance(v, str) else P.pg_case_id(v))
+def test_kv8_attention_on_structured_score_profiles(hip, shape, cv):
+    """g2v_decode_attn_pg_kv8 on every family of tests/attn_profile_check.py at the shapes P.PG_SHAPES, the rows through the
+    host quantiser: poison at and behind the new row, the appended row's scale bit-equal and its values equal to the quantised
+    row of qknorm_mrope_cache, the rows below untouched, and the output inside the hard and the sharp bound against fp64
+    attention over the dequantised cache; an exact case (peak 200) equals the peak key's dequantised V row bit for bit."""
+    case, variant = cv
+    Hq, Hkv, cap, lens = P.PG_SHAPES[shape]
+    B, G = len(lens), Hq // Hkv
+    new = P.new_row_slots(case, lens, variant)
+    s = make_step(hip, lens, Hq, Hkv, 60 + B + variant, cap=cap, edit=lambda qkv: P.align_new_k(qkv, Hq, Hkv, new))
+    # the step's q and its new rows in bf16, from the separate kernel
+    qn = torch.empty((B, Hq * 128), dtype=torch.bfloat16, device="cuda")
+    k3, v3 = s["k16"].cuda(), s["v16"].cuda()
+    at = torch.tensor([z * cap + n - 1 for z, n in enumerate(lens)], dtype=torch.int32, device="cuda")
+    hip.qknorm_mrope_cache(s["qkv"], Hq, Hkv, s["qw"], s["qw"], s["kw"], s["kw"], 0, 1e-6, 1, s["cos"], s["sin"], qn, k3, v3, at)
+    torch.cuda.synchronize()
+    qn, k3, v3 = qn.cpu(), k3.cpu(), v3.cpu()
+    knew = roundtrip(torch.stack([k3[z, n - 1] for z, n in enumerate(lens)]))
+    waves = P.pg_waves(cap, P.pg_nbh(Hkv, B))
+    Ks, Vs, infos = P.build_step(case, qn, knew, lens, Hq, Hkv, waves, 61 + variant, variant, quant=roundtrip)
+    kc, vc, ks, vs = (s[n].cpu() for n in ("kc", "vc", "ks", "vs"))
+    for z, n in enumerate(lens):
+        if n > 1:
+            kc[z, :n - 1], ks[z, :n - 1] = host_quant(Ks[z])
+            vc[z, :n - 1], vs[z, :n - 1] = host_quant(Vs[z])
+            assert torch.equal(host_dequant(kc[z, :n - 1], ks[z, :n - 1]), Ks[z])      # the builder's rows ARE cache values
+        assert (kc[z, n - 1:] == POISON).all() and (vc[z, n - 1:] == POISON).all(), z
+        assert torch.isnan(ks[z, n - 1:]).all() and torch.isnan(vs[z, n - 1:]).all(), z
+    if case in (("rise", 20.0), ("fall", 20.0)) and lens[0] > 2000:
+        nsc = int(torch.unique(ks[0, :lens[0] - 1, 0]).numel())
+        assert nsc >= 6, nsc
+    for n_, t in (("kc", kc), ("vc", vc), ("ks", ks), ("vs", vs)):
+        s[n_] = t.cuda()
+    out = run_kv8(hip, s, Hq, Hkv)
+    torch.cuda.synchronize()
+    kc1, vc1, ks1, vs1 = (s[n].cpu() for n in ("kc", "vc", "ks", "vs"))
+    out = out.cpu()
+    name, over = f"attn_pg_kv8 {shape} {P.case_id(case)}", 0
+    for z, n in enumerate(lens):
+        assert torch.equal(kc1[z, :n - 1], kc[z, :n - 1]) and torch.equal(vc1[z, :n - 1], vc[z, :n - 1]), z
+        assert torch.equal(ks1[z, :n - 1], ks[z, :n - 1]) and torch.equal(vs1[z, :n - 1], vs[z, :n - 1]), z
+        assert (kc1[z, n:] == POISON).all() and (vc1[z, n:] == POISON).all(), z
+        assert torch.isnan(ks1[z, n:]).all() and torch.isnan(vs1[z, n:]).all(), z
+        for got_c, got_s, row in ((kc1, ks1, k3[z, n - 1]), (vc1, vs1, v3[z, n - 1])):
+            qh, sh = host_quant(row)
+            assert torch.equal(got_s[z, n - 1].view(torch.int32), sh.view(torch.int32)), z
+            assert torch.equal(host_dequant(got_c[z, n - 1], got_s[z, n - 1]), host_dequant(qh, sh)), z
+        K, V = host_dequant(kc1[z, :n], ks1[z, :n]), host_dequant(vc1[z, :n], vs1[z, :n])
+        o = out[z].view(Hq, 128)
+        over += P.check_slot(PROFILE, name, case[0], o, qn[z].view(Hq, 128), K, V, Hkv)
+        for h in range(Hkv):
+            if infos[z][h]["exact"]:
+                want = V[infos[z][h]["peak"], h].expand(G, 128)
+                assert torch.equal(o[h * G:(h + 1) * G].view(torch.int16), want.view(torch.int16)), (z, h)
+    w = PROFILE.worst[name]
+    print(f"[{name}] |err| / hard {w['hard']:.3f}  |err| / sharp {w['sharp']:.3f}")
+    assert over == 0, (name, over, w)
