@@ -212,20 +212,116 @@ def point_cloud_mask(pred_dict, conf_threshold=None, edge_rtol=None, edge_atol=N
     return hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan).view(torch.bool)
 
 
-def save_point_cloud(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_atol=None, filter_nan=True, verbose=True):
+def _voxel_args(voxel_size, origin, min_points):
+    """(voxel_size as a float, origin as three floats or None, min_points), or ValueError: before any launch"""
+    try:
+        v = float(voxel_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"voxel_size must be a number > 0, got {voxel_size!r}") from None
+    if not (v > 0.0 and np.isfinite(v)):
+        raise ValueError(f"voxel_size must be finite and > 0, got {voxel_size}")
+    if isinstance(min_points, bool) or not isinstance(min_points, (int, np.integer)) or min_points < 1:
+        raise ValueError(f"min_points must be an integer >= 1, got {min_points}")
+    if origin is not None:
+        origin = [float(o) for o in (origin.tolist() if hasattr(origin, "tolist") else origin)]
+        if len(origin) != 3 or not all(np.isfinite(o) for o in origin):
+            raise ValueError(f"origin must be three finite numbers, got {origin}")
+    return v, origin, int(min_points)
+
+
+def _voxel_mask(mask, shape, device):
+    """An explicit mask as uint8 [N,H,W] on the device, or ValueError"""
+    if not torch.is_tensor(mask):
+        raise ValueError(f"mask: a bool / uint8 tensor [N,H,W] = {tuple(shape)} expected, got {type(mask).__name__}")
+    if mask.dim() == 4 and mask.shape[0] == 1:
+        mask = mask[0]
+    if tuple(mask.shape) != tuple(shape) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"mask: bool / uint8 [N,H,W] = {tuple(shape)} expected, got {mask.dtype} {tuple(mask.shape)}")
+    mask = mask.to(device).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _voxel_run(points, images, mask, v, origin, min_points):
+    """assign + reduce on the device tensors: dict(records, points, colors, counts, origin, num_input_points).  ValueError, with
+    nothing written, where a point falls outside the 2^21 cells per axis that the grid has."""
+    from . import hip
+    lo = hi = None
+    if origin is None:
+        # Open3D's convention for voxel_down_sample: the minimum bound of the cloud minus half a voxel, formed in fp64
+        lo, hi, n = hip.voxel_bounds(points, mask)
+        origin = [x - v * 0.5 for x in lo] if n else [0.0, 0.0, 0.0]
+    voxel_of, (m, n_in, n_out, status) = hip.voxel_assign(points, mask, v, origin)
+    if n_out or status:
+        if lo is None:
+            lo, hi, _ = hip.voxel_bounds(points, mask)
+        raise ValueError(f"voxel_size {v} is too small for this cloud: {n_out} of its points lie outside the grid's 2^21 cells per "
+                         f"axis around the origin {origin} (extent of the points: min {lo}, max {hi}; status {status})")
+    records, counts, out_points, out_colors = hip.voxel_reduce(points, images, voxel_of, m, v, origin)
+    if min_points > 1:                                      # on the [M]-sized outputs: M is small
+        keep = counts >= min_points
+        records, counts, out_points, out_colors = records[keep], counts[keep], out_points[keep], out_colors[keep]
+    return dict(records=records, points=out_points, colors=out_colors, counts=counts, origin=tuple(origin), num_input_points=n_in)
+
+
+def _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan):
+    from . import hip
+    if filter_nan or conf is not None or edge_rtol is not None or edge_atol is not None:
+        return hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan)
+    return torch.ones(points.shape[:3], dtype=torch.uint8, device=points.device)
+
+
+def voxel_downsample(pred_dict, voxel_size, origin=None, min_points=1, conf_threshold=None, edge_rtol=None, edge_atol=None,
+                     filter_nan=True, mask=None):
+    """The cloud of a recon result with one vertex per occupied cell of a regular grid, on the device (hip.voxel_assign /
+    voxel_reduce; DESIGN.md 6j has the exact rule): the vertex is the mean of the cell's points, its colour the mean of their
+    colour bytes, rounded half up; cells come in the order in which the pixels (view-major, row-major) first reach them.
+    The pixels are those point_cloud_mask keeps under the same filter arguments; an explicit mask (bool / uint8 [N,H,W])
+    replaces the filters.  Non-finite points never take part.  min_points drops cells with fewer points.
+    origin: a corner of the grid (cells are [origin + k v, origin + (k + 1) v)); pass the same one to put two scenes on one grid.
+    None takes the convention of Open3D's voxel_down_sample - the per-axis minimum of the participating points minus
+    voxel_size / 2, in fp64.  Open3D itself is not a dependency and nothing here is tested against it: the convention is followed,
+    equality with its output is not claimed.
+    Returns dict(points fp32 [M,3], colors uint8 [M,3], counts int32 [M], origin (3 floats), num_input_points).  ValueError if
+    the voxel size is so small that a point lies more than 2^20 cells from the origin."""
+    v, origin, min_points = _voxel_args(voxel_size, origin, min_points)
+    if mask is not None:
+        points, _, _, images, _ = _cloud_inputs(pred_dict, None, None, None, need_images=True)
+        mask = _voxel_mask(mask, points.shape[:3], points.device)
+    else:
+        points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=True)
+        mask = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    out = _voxel_run(points, images, mask, v, origin, min_points)
+    del out["records"]
+    return out
+
+
+def save_point_cloud(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_atol=None, filter_nan=True, verbose=True,
+                     voxel_size=None, voxel_origin=None, min_points=1):
     """save_ply_visualization's PLY with the filters of point_cloud_mask, packed on the device: mask, stable compaction into
     15-byte records, ONE device-to-host copy of the kept records, one write.  With every filter but filter_nan off the file is
-    byte-identical to save_ply_visualization's.  Returns dict(num_points, counts = kept pixels per view)."""
+    byte-identical to save_ply_visualization's.  Returns dict(num_points, counts = kept pixels per view).
+    voxel_size: the kept pixels are voxel-downsampled first (voxel_downsample; voxel_origin and min_points are its origin and
+    min_points) and only the cells' records are copied and written; the dict then also has num_input_points, and num_points is
+    the number of records written."""
     from . import hip
+    if voxel_size is not None:
+        voxel_size, voxel_origin, min_points = _voxel_args(voxel_size, voxel_origin, min_points)
     points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=True)
-    if filter_nan or conf is not None or edge_rtol is not None or edge_atol is not None:
-        mask = hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan)
+    mask = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    if voxel_size is not None:
+        vox = _voxel_run(points, images, mask, voxel_size, voxel_origin, min_points)
+        records = vox["records"]
+        counts = hip.cloud_counts(points, images, mask)
     else:
-        mask = torch.ones(points.shape[:3], dtype=torch.uint8, device=points.device)
-    records, counts = hip.cloud_compact(points, images, mask)
+        records, counts = hip.cloud_compact(points, images, mask)
     os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
     host.write_ply_records(save_path, records.cpu())
     counts = counts.cpu().tolist()
+    if voxel_size is not None:
+        if verbose:
+            print(f"{save_path}: {records.shape[0]} voxels of {voxel_size} from {vox['num_input_points']} of {mask.numel()} points, "
+                  f"per view {counts}")
+        return dict(num_points=int(records.shape[0]), counts=counts, num_input_points=vox["num_input_points"])
     if verbose:
         print(f"{save_path}: {records.shape[0]} of {mask.numel()} points kept, per view {counts}")
     return dict(num_points=int(records.shape[0]), counts=counts)

@@ -40,7 +40,7 @@ class GemmDesc(C.Structure):
                 ("flags", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
+_P, _I, _F, _L, _D = C.c_void_p, C.c_int, C.c_float, C.c_int64, C.c_double
 _SIGS = {
     "g2v_version": ([], C.c_int),
     "g2v_arch": ([], C.c_char_p),
@@ -108,6 +108,11 @@ _SIGS = {
     "g2v_cloud_compact": ([_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P], C.c_int),
     "g2v_intrinsics_lsq_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_intrinsics_lsq": ([_P, _P, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
+    "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_voxel_reduce_workspace": ([_L], C.c_int64),
+    "g2v_voxel_reduce": ([_P, _P, _P, _I, _I, _I, _D, _D, _D, _D, _L, _P, _P, _P, _P, _P, _L, _I, _P], C.c_int),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -1000,6 +1005,18 @@ def cloud_compact(points, colors, mask, workspace=None):
     return records[:m], counts
 
 
+def cloud_counts(points, colors, mask, workspace=None):
+    """counts int32 [N] of cloud_compact alone: g2v_cloud_compact with room for no record (it then only counts)."""
+    N, H, W = _nhw3(points, "points")
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    if workspace is None:
+        workspace = _cloud_workspace(cloud_compact_workspace(N, H, W), points.device, "compact")
+    counts = torch.empty(N, dtype=torch.int32, device=points.device)
+    _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(mask), N, H, W, None, 0, _p(counts), _p(workspace),
+                                workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_compact")
+    return counts
+
+
 def intrinsics_lsq_workspace(N, H, W):
     return int(lib().g2v_intrinsics_lsq_workspace(int(N), int(H), int(W)))
 
@@ -1021,6 +1038,79 @@ def intrinsics_lsq(local, mask=None, workspace=None):
     _ck(lib().g2v_intrinsics_lsq(_p(local), _p(mask), N, H, W, _p(K), _p(used), _p(workspace),
                                  workspace.numel() * workspace.element_size(), _stream()), "g2v_intrinsics_lsq")
     return K, used
+
+
+# ------------------------------------------------------------------------------------------ voxel downsampling (csrc/voxel.hip)
+VOXEL_NO_RUNS = 1                                           # G2V_VOXEL_NO_RUNS (A/B only)
+
+
+def _voxel_inputs(points, mask):
+    N, H, W = _nhw3(points, "points")
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    return N, H, W, mask
+
+
+def voxel_bounds(points, mask):
+    """(min fp64 [3], max fp64 [3], count) of the points that take part (mask != 0, finite), as python floats (g2v_voxel_bounds).
+    Synchronous: one readback of seven words.  count == 0: zeros."""
+    N, H, W, mask = _voxel_inputs(points, mask)
+    out = torch.empty(7, dtype=torch.float32, device=points.device)
+    _ck(lib().g2v_voxel_bounds(_p(points), _p(mask), N, H, W, _p(out), _stream()), "g2v_voxel_bounds")
+    host = out.cpu()
+    lo_hi = host[:6].double().tolist()
+    return lo_hi[:3], lo_hi[3:], int(host[6:].view(torch.int32).item())
+
+
+def voxel_assign_workspace(N, H, W):
+    return int(lib().g2v_voxel_assign_workspace(int(N), int(H), int(W)))
+
+
+def voxel_reduce_workspace(M):
+    return int(lib().g2v_voxel_reduce_workspace(int(M)))
+
+
+def voxel_assign(points, mask, voxel_size, origin, workspace=None):
+    """The dense id of every pixel's grid cell (g2v_voxel_assign): points fp32 [N,H,W,3], mask uint8 or bool [N,H,W], voxel_size
+    > 0 and origin (3 floats), both taken as fp64 -> (voxel_of int32 [N,H,W], -1 where the pixel is dropped; stats = [cells M,
+    participating pixels, out-of-range pixels, status]).  Cells are numbered by first appearance in flat pixel order.
+    Synchronous: the four stats are read back once."""
+    N, H, W, mask = _voxel_inputs(points, mask)
+    ox, oy, oz = (float(o) for o in origin)
+    nbytes = voxel_assign_workspace(N, H, W)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, points.device, "voxel_assign")
+    voxel_of = torch.empty((N, H, W), dtype=torch.int32, device=points.device)
+    stats = torch.empty(4, dtype=torch.int32, device=points.device)
+    _ck(lib().g2v_voxel_assign(_p(points), _p(mask), N, H, W, float(voxel_size), ox, oy, oz, _p(voxel_of), _p(stats), _p(workspace),
+                               workspace.numel() * workspace.element_size(), _stream()), "g2v_voxel_assign")
+    return voxel_of, stats.tolist()
+
+
+def voxel_reduce(points, colors, voxel_of, M, voxel_size, origin, workspace=None, flags=0):
+    """The cells' vertices (g2v_voxel_reduce): voxel_of and M = stats[0] from voxel_assign with the same points, voxel_size and
+    origin; colors fp32 [N,3,H,W] -> (records uint8 [M,15] = <f4 x,y,z + u1 r,g,b, counts int32 [M], points fp32 [M,3], colors
+    uint8 [M,3])."""
+    N, H, W = _nhw3(points, "points")
+    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
+        "colors: fp32 [N,3,H,W], contiguous"
+    assert voxel_of.is_cuda and voxel_of.dtype == torch.int32 and tuple(voxel_of.shape) == (N, H, W) and voxel_of.is_contiguous(), \
+        "voxel_of: int32 [N,H,W]"
+    M = int(M)
+    ox, oy, oz = (float(o) for o in origin)
+    dev = points.device
+    records = torch.empty((M, 15), dtype=torch.uint8, device=dev)
+    counts = torch.empty(M, dtype=torch.int32, device=dev)
+    out_points = torch.empty((M, 3), dtype=torch.float32, device=dev)
+    out_colors = torch.empty((M, 3), dtype=torch.uint8, device=dev)
+    nbytes = voxel_reduce_workspace(M)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, dev, "voxel_reduce")
+    _ck(lib().g2v_voxel_reduce(_p(points), _p(colors), _p(voxel_of), N, H, W, float(voxel_size), ox, oy, oz, M, _p(records), _p(counts),
+                               _p(out_points), _p(out_colors), _p(workspace), workspace.numel() * workspace.element_size(), int(flags),
+                               _stream()), "g2v_voxel_reduce")
+    return records, counts, out_points, out_colors
 
 
 def mrope_table_into(pos_i32, inv_freq, cos, sin):

@@ -435,6 +435,38 @@ int g2v_cloud_compact(const void* points, const void* colors, const void* mask, 
 int64_t g2v_intrinsics_lsq_workspace(int N, int H, int W);
 int g2v_intrinsics_lsq(const void* local, const void* mask, int N, int H, int W, void* K, void* used, void* workspace,
                        int64_t workspace_bytes, void* stream);
+
+/* ---- voxel-grid downsampling of the cloud (csrc/voxel.hip) ------------------------------------------------------------------
+ * One vertex per occupied cell of the grid origin + k * voxel_size: the mean of the cell's points and of their colour bytes.
+ * points fp32 [N,H,W,3], colors fp32 [N,3,H,W], mask u8 [N,H,W].  A pixel takes part if mask != 0 and its three coordinates are
+ * finite.  Per axis, in fp64 without contraction: t = ((double)p - o) / v, g = floor(t); the pixel is out of range (dropped and
+ * counted) unless -2^20 <= g < 2^20; q = (int64)floor((t - g) * 2^24 + 0.5).  Per cell: n points, S = sum q, C = sum of the
+ * colour bytes of g2v_cloud_compact; the vertex is (float)(o + ((double)g + (double)S / ((double)n * 2^24)) * v) and the colour
+ * byte (2 C + n) / (2 n), which rounds half up.  Cells are numbered in the order of the flat pixel index (view-major, row-major)
+ * of their first participating pixel.  Every sum is an integer sum: the same inputs give the same bytes on every run.
+ * Every entry point returns -22 before any launch on a NULL required pointer, on N, H or W <= 0, on N*H*W >= 2^31, on a voxel
+ * size that is not > 0 or not finite, on a non-finite origin, on M < 0 and on a workspace smaller than its query says (8-byte
+ * aligned, no initialisation needed).  The queries return 0 for what the entry points refuse.  hipGraph-capturable.
+ *
+ * g2v_voxel_bounds: bounds[0..2] / [3..5] = the fp32 minimum / maximum per axis of the participating points, bounds[6] (int32)
+ *   their number (0: the six floats are 0).
+ * g2v_voxel_assign: voxel_of int32 [N,H,W] = the dense id of the pixel's cell, -1 for a pixel that is dropped; stats int32 [4] =
+ *   {cells M, participating pixels, out-of-range pixels, status (non-zero: a probe ran out of slots; never with the table this
+ *   sizes, which holds at least 2 N H W slots)}.
+ * g2v_voxel_reduce: records u8 [M,15] (the PLY record of g2v_cloud_compact), counts int32 [M] = points per cell and, where the
+ *   pointers are not NULL, out_points fp32 [M,3] and out_colors u8 [M,3]; voxel_of, voxel_size and origin as given to / made by
+ *   g2v_voxel_assign, M = its stats[0] (ids >= M are ignored).  M == 0 is a valid no-op.  G2V_VOXEL_NO_RUNS (A/B only): every
+ *   pixel issues its own atomics; without it the lanes of a wave that share a cell are summed first.  The result is the same.  */
+#define G2V_VOXEL_NO_RUNS 1
+int g2v_voxel_bounds(const void* points, const void* mask, int N, int H, int W, void* bounds, void* stream);
+int64_t g2v_voxel_assign_workspace(int N, int H, int W);
+int g2v_voxel_assign(const void* points, const void* mask, int N, int H, int W, double voxel_size, double origin_x,
+                     double origin_y, double origin_z, void* voxel_of, void* stats, void* workspace, int64_t workspace_bytes,
+                     void* stream);
+int64_t g2v_voxel_reduce_workspace(int64_t M);
+int g2v_voxel_reduce(const void* points, const void* colors, const void* voxel_of, int N, int H, int W, double voxel_size,
+                     double origin_x, double origin_y, double origin_z, int64_t M, void* records, void* counts, void* out_points,
+                     void* out_colors, void* workspace, int64_t workspace_bytes, int flags, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@ Fixes the reference's Namespace-as-path bug and sorts the folder listing (SURVEY
 
 Flags of this project's own, all off by default (without them main() does what the reference's does): --conf-threshold,
 --edge-rtol, --edge-atol write the PLY through save_point_cloud's device filters; --intrinsics fits and prints a pinhole
-matrix per view."""
+matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cloud on the device before it is written."""
 import argparse
 import os
 import sys
@@ -21,6 +21,9 @@ parser.add_argument("--edge-rtol", type=float, default=None, metavar="R",
                     help="drop depth discontinuities: 3x3 depth range / depth above R (0.03 is the usual choice)")
 parser.add_argument("--edge-atol", type=float, default=None, metavar="A", help="drop depth discontinuities: 3x3 depth range above A")
 parser.add_argument("--intrinsics", action="store_true", help="fit, print and return a pinhole matrix per view (pred['intrinsics'])")
+parser.add_argument("--voxel-size", type=float, default=None, metavar="V",
+                    help="voxel-downsample the cloud on the device: one vertex per occupied cell of a grid of spacing V")
+parser.add_argument("--voxel-min-points", type=int, default=1, metavar="K", help="with --voxel-size: drop cells with fewer than K points")
 
 
 def main(argv=None):
@@ -31,9 +34,10 @@ def main(argv=None):
     model, tokenizer, new_token_ids, vit_image_transform, dino_transform = load_model_and_tokenizer(args.model_path)
     pred = model.recon(tokenizer, new_token_ids, dino_transform, image_names)
     filtered = args.conf_threshold is not None or args.edge_rtol is not None or args.edge_atol is not None
-    if filtered:
+    if filtered or args.voxel_size is not None:
         from g2vlm_utils import save_point_cloud
-        save_point_cloud(pred, args.save_path, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol)
+        save_point_cloud(pred, args.save_path, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol,
+                         voxel_size=args.voxel_size, min_points=args.voxel_min_points)
     else:
         save_ply_visualization(pred, args.save_path)
     if args.intrinsics:
