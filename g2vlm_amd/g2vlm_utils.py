@@ -200,16 +200,98 @@ def _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images):
     return points[0].detach().float().contiguous(), local[0].detach().float().contiguous(), conf, images, logit
 
 
-def point_cloud_mask(pred_dict, conf_threshold=None, edge_rtol=None, edge_atol=None, filter_nan=True):
+def point_cloud_mask(pred_dict, conf_threshold=None, edge_rtol=None, edge_atol=None, filter_nan=True, min_views=None,
+                     max_in_front=None, depth_rtol=0.03, intrinsics=None):
     """Which pixels of a recon result belong in the cloud: bool [N,H,W] on the device (hip.cloud_mask).
     filter_nan: the world point is finite.  conf_threshold: a probability p in (0,1); keeps sigmoid(conf) > p, evaluated as
     conf > log(p/(1-p)).  edge_rtol / edge_atol: drops depth discontinuities ("flying pixels") by the reference's depth_edge
-    rule on the local depth (modeling/pi3/utils/geometry.py:339, 3x3 window)."""
+    rule on the local depth (modeling/pi3/utils/geometry.py:339, 3x3 window).
+    min_views / max_in_front: the multi-view consistency filter on top of those (multiview_consistency has the rule; depth_rtol
+    and intrinsics are its arguments): a pixel stays only if at least min_views other views confirm its point and at most
+    max_in_front other views see it floating in front of their surface.  Both None: no such filter, no camera_poses needed."""
     from . import hip
+    if min_views is not None or max_in_front is not None:
+        min_views, max_in_front = _consistency_args(min_views, max_in_front, depth_rtol)
+        points, local, conf, _, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=False)
+        poses = _consistency_poses(pred_dict, points.shape[0])
+        K = _consistency_K(intrinsics, points.shape[0])
+        base = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+        if K is None:
+            K, _ = hip.intrinsics_lsq(local, base)
+        return hip.cloud_consistency(points, local, base, poses, K.to(points.device), depth_rtol, min_views, max_in_front)[2].view(torch.bool)
     points, local, conf, _, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=False)
     if not (filter_nan or conf is not None or edge_rtol is not None or edge_atol is not None):
         return torch.ones(points.shape[:3], dtype=torch.bool, device=points.device)
     return hip.cloud_mask(points, local, conf, logit or 0.0, edge_atol, edge_rtol, finite=filter_nan).view(torch.bool)
+
+
+def _consistency_args(min_views, max_in_front, depth_rtol):
+    """(min_agree, max_in_front) as the kernel takes them, or ValueError: before any launch"""
+    def integer(x):
+        return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+    if min_views is not None and not (integer(min_views) and 1 <= min_views <= 255):
+        raise ValueError(f"min_views must be an integer in [1, 255], got {min_views!r}")
+    if max_in_front is not None and not (integer(max_in_front) and 0 <= max_in_front <= 255):
+        raise ValueError(f"max_in_front must be an integer in [0, 255], got {max_in_front!r}")
+    try:
+        ok = float(depth_rtol) >= 0.0 and np.isfinite(float(depth_rtol))
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"depth_rtol must be finite and >= 0, got {depth_rtol!r}")
+    return (0 if min_views is None else int(min_views)), (-1 if max_in_front is None else int(max_in_front))
+
+
+def _consistency_poses(pred_dict, n):
+    poses = pred_dict.get("camera_poses")
+    if not torch.is_tensor(poses) or tuple(poses.shape) != (1, n, 4, 4):
+        raise ValueError(f"the multi-view filter needs pred_dict['camera_poses'] [1,N,4,4] with N = {n}, got "
+                         f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    if n > 256:
+        raise ValueError(f"the multi-view filter takes at most 256 views (its counts are bytes), got {n}")
+    return poses[0].detach().float().contiguous()
+
+
+def _consistency_K(intrinsics, n):
+    if intrinsics is None:
+        return None
+    if not torch.is_tensor(intrinsics) or tuple(intrinsics.shape) not in ((1, n, 3, 3), (n, 3, 3)):
+        raise ValueError(f"intrinsics: a tensor [1,N,3,3] or [N,3,3] with N = {n} expected, got "
+                         f"{tuple(intrinsics.shape) if torch.is_tensor(intrinsics) else type(intrinsics).__name__}")
+    return intrinsics.detach().float().reshape(n, 3, 3).contiguous()
+
+
+def multiview_consistency(pred_dict, depth_rtol=0.03, intrinsics=None, conf_threshold=None, edge_rtol=None, edge_atol=None,
+                          filter_nan=True, mask=None):
+    """Does any other view see this point?  On the device (hip.cloud_consistency; include/g2vlm_hip.h and DESIGN.md 6k have the
+    exact rule): the world point of every pixel of view i is projected into every other view j with j's pose and pinhole K and
+    compared with the depth j predicts at the pixel it falls in (nearest neighbour).  It AGREES if the two depths differ by at
+    most depth_rtol times j's depth, lies IN FRONT if it is nearer to camera j than that - in the free space before the surface j
+    sees - and counts as neither where it is behind (occluded), outside j's image or on a pixel j's mask drops.
+    The pixels that take part, as sources and as targets, are those point_cloud_mask keeps under the same filter arguments; an
+    explicit mask (bool / uint8 [N,H,W]) replaces the filters.  intrinsics: [1,N,3,3] or [N,3,3]; None takes
+    estimate_intrinsics(pred_dict, that mask) - a view whose K has a NaN entry then confirms nobody.
+    Returns dict(agree uint8 [N,H,W], in_front uint8 [N,H,W] = the number of other views in each class, covisibility int32
+    [N,N,2] = per (i, j) the pixels of i that agree / lie in front in j, intrinsics fp32 [1,N,3,3], mask bool [N,H,W] = the base
+    mask), all on the device.  Needs pred_dict["camera_poses"] [1,N,4,4]; at most 256 views."""
+    from . import hip
+    _consistency_args(None, None, depth_rtol)
+    if mask is not None:
+        points, local, _, _, _ = _cloud_inputs(pred_dict, None, None, None, need_images=False)
+    else:
+        points, local, conf, _, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=False)
+    n = points.shape[0]
+    poses = _consistency_poses(pred_dict, n)
+    K = _consistency_K(intrinsics, n)
+    if mask is not None:
+        base = _voxel_mask(mask, points.shape[:3], points.device)
+    else:
+        base = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    if K is None:
+        K, _ = hip.intrinsics_lsq(local, base)
+    K = K.to(points.device)
+    agree, in_front, _, pairs = hip.cloud_consistency(points, local, base, poses, K, depth_rtol, pairs=True)
+    return dict(agree=agree, in_front=in_front, covisibility=pairs, intrinsics=K.unsqueeze(0), mask=base.view(torch.bool))
 
 
 def _voxel_args(voxel_size, origin, min_points):
@@ -303,11 +385,26 @@ def save_point_cloud(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, 
     voxel_size: the kept pixels are voxel-downsampled first (voxel_downsample; voxel_origin and min_points are its origin and
     min_points) and only the cells' records are copied and written; the dict then also has num_input_points, and num_points is
     the number of records written."""
-    from . import hip
     if voxel_size is not None:
         voxel_size, voxel_origin, min_points = _voxel_args(voxel_size, voxel_origin, min_points)
     points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=True)
     mask = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    return _save_masked(points, images, mask, save_path, verbose, voxel_size, voxel_origin, min_points)
+
+
+def save_point_cloud_masked(pred_dict, save_path, mask, verbose=True, voxel_size=None, voxel_origin=None, min_points=1):
+    """save_point_cloud for an explicit mask (bool / uint8 [N,H,W], e.g. point_cloud_mask(min_views=...)'s) in place of the
+    filter arguments: the same compaction, the same optional voxel downsampling, the same file and the same returned dict."""
+    if voxel_size is not None:
+        voxel_size, voxel_origin, min_points = _voxel_args(voxel_size, voxel_origin, min_points)
+    points, _, _, images, _ = _cloud_inputs(pred_dict, None, None, None, need_images=True)
+    mask = _voxel_mask(mask, points.shape[:3], points.device)
+    return _save_masked(points, images, mask, save_path, verbose, voxel_size, voxel_origin, min_points)
+
+
+def _save_masked(points, images, mask, save_path, verbose, voxel_size, voxel_origin, min_points):
+    """the export of checked inputs: compaction (or voxel downsampling) of the pixels mask keeps, one copy, one write"""
+    from . import hip
     if voxel_size is not None:
         vox = _voxel_run(points, images, mask, voxel_size, voxel_origin, min_points)
         records = vox["records"]

@@ -108,6 +108,8 @@ _SIGS = {
     "g2v_cloud_compact": ([_P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P], C.c_int),
     "g2v_intrinsics_lsq_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_intrinsics_lsq": ([_P, _P, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_consistency_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_cloud_consistency": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
@@ -1038,6 +1040,38 @@ def intrinsics_lsq(local, mask=None, workspace=None):
     _ck(lib().g2v_intrinsics_lsq(_p(local), _p(mask), N, H, W, _p(K), _p(used), _p(workspace),
                                  workspace.numel() * workspace.element_size(), _stream()), "g2v_intrinsics_lsq")
     return K, used
+
+
+def cloud_consistency_workspace(N, H, W):
+    return int(lib().g2v_cloud_consistency_workspace(int(N), int(H), int(W)))
+
+
+def cloud_consistency(points, local, mask, poses, K, depth_rtol, min_agree=0, max_in_front=-1, pairs=False, workspace=None):
+    """Per pixel, in how many OTHER views its world point is confirmed / floats in front of the surface (g2v_cloud_consistency;
+    include/g2vlm_hip.h has the exact rule): points, local fp32 [N,H,W,3], mask uint8 or bool [N,H,W] or None (all pixels), poses
+    fp32 [N,4,4] camera-to-world, K fp32 [N,3,3], N <= 256.  Returns (agree uint8 [N,H,W], in_front uint8 [N,H,W], mask_out
+    uint8 [N,H,W] = eligible and agree >= min_agree and (max_in_front < 0 or in_front <= max_in_front), pairs int32 [N,N,2] or
+    None).  Bit-reproducible; no host synchronisation."""
+    N, H, W = _nhw3(points, "points")
+    assert _nhw3(local, "local") == (N, H, W), "local: the shape of points"
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    for t, shape, what in ((poses, (N, 4, 4), "poses"), (K, (N, 3, 3), "K")):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous(), f"{what}: fp32 {list(shape)}, contiguous"
+    dev = points.device
+    nbytes = cloud_consistency_workspace(N, H, W)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, dev, "consistency")
+    agree = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    in_front = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    mask_out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    pair_counts = torch.empty((N, N, 2), dtype=torch.int32, device=dev) if pairs else None
+    _ck(lib().g2v_cloud_consistency(_p(points), _p(local), _p(mask), _p(poses), _p(K), N, H, W, float(depth_rtol), int(min_agree),
+                                    int(max_in_front), _p(agree), _p(in_front), _p(pair_counts), _p(mask_out), _p(workspace),
+                                    workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_consistency")
+    return agree, in_front, mask_out, pair_counts
 
 
 # ------------------------------------------------------------------------------------------ voxel downsampling (csrc/voxel.hip)

@@ -3,9 +3,10 @@ inference_chat.py:8, the notebook): `from g2vlm_utils import load_model_and_toke
 root on `sys.path` in place of the reference's.  The implementation lives in g2vlm_amd/g2vlm_utils.py; this file only
 re-exports it under the reference's name (reference g2vlm_utils.py:31-149), with the filtered export that this project adds."""
 from g2vlm_amd.g2vlm_utils import (LazySafetensors, add_special_tokens, build_model, build_transform,  # noqa: F401
-                                   configs_from_dims, estimate_intrinsics, load_model_and_tokenizer, pil_img2rgb,
-                                   point_cloud_mask, process_conversation, save_ply_visualization, save_point_cloud,
-                                   voxel_downsample)
+                                   configs_from_dims, estimate_intrinsics, load_model_and_tokenizer, multiview_consistency,
+                                   pil_img2rgb, point_cloud_mask, process_conversation, save_ply_visualization, save_point_cloud,
+                                   save_point_cloud_masked, voxel_downsample)
 
 __all__ = ["load_model_and_tokenizer", "build_transform", "process_conversation", "save_ply_visualization",
-           "save_point_cloud", "point_cloud_mask", "estimate_intrinsics", "voxel_downsample"]
+           "save_point_cloud", "point_cloud_mask", "estimate_intrinsics", "voxel_downsample", "multiview_consistency",
+           "save_point_cloud_masked"]

@@ -436,6 +436,36 @@ int64_t g2v_intrinsics_lsq_workspace(int N, int H, int W);
 int g2v_intrinsics_lsq(const void* local, const void* mask, int N, int H, int W, void* K, void* used, void* workspace,
                        int64_t workspace_bytes, void* stream);
 
+/* ---- multi-view consistency of the cloud (csrc/consistency.hip): does any other view see this point? ------------------------
+ * points / local fp32 [N,H,W,3] as above (of local only the depth local[..., 2] is read), mask u8 [N,H,W] or NULL (all pixels),
+ * poses fp32 [N,4,4] camera-to-world (R = poses[j,:3,:3], t = poses[j,:3,3]), K fp32 [N,3,3] (fx = K[j,0,0], fy = K[j,1,1],
+ * cx = K[j,0,2], cy = K[j,1,2]; g2v_intrinsics_lsq's), depth_rtol >= 0.
+ *
+ * The rule is exact: fp32 throughout, every operation rounded once, no fused multiply-add, every comparison an IEEE compare
+ * (false on NaN).  For a source pixel (i, p) with world point P and every target view j != i:
+ *   d = P - t;  q_k = (R[0][k] d0 + R[1][k] d1) + R[2][k] d2  (k = 0, 1, 2: R^T d, parenthesised as written);
+ *   u = fx (q0 / q2) + cx,  v = fy (q1 / q2) + cy, the divisions correctly rounded;
+ *   inside iff q2 > 0 && u >= 0 && u < W && v >= 0 && v < H; only then x = (int)u, y = (int)v (pixel centres are at + 0.5, so
+ *   the pixel that contains u is floor(u): a nearest-neighbour lookup) and zt = local[j,y,x,2];
+ *   valid iff inside, mask[j,y,x] != 0, zt finite and zt > 0;  tol = depth_rtol zt, diff = q2 - zt;
+ *   AGREE iff valid and |diff| <= tol;  IN FRONT iff valid and diff < -tol (P floats between camera j and the surface j sees).
+ *   A point behind the surface is merely occluded: neither.
+ * A source pixel is eligible iff mask[i,p] != 0 and P is finite; a pixel that is not has both counts 0.
+ *
+ * Outputs, each optional (NULL) but not all four at once: agree / in_front u8 [N,H,W] = the number of target views in each
+ * class; pairs int32 [N,N,2], pairs[i,j,0] / [i,j,1] = the pixels of view i that agree / lie in front in view j (diagonal 0;
+ * integer atomics: the same on every run); mask_out u8 [N,H,W] = eligible && agree >= min_agree && (max_in_front < 0 ||
+ * in_front <= max_in_front).  The workspace (4 N H W bytes, no initialisation needed) receives a depth plane: local z where
+ * valid, NaN elsewhere.  -22 before any launch for the section's reasons above, for N > 256 (the counts are bytes), for
+ * H > 524280 (8 rows per tile, 65535 tile rows per launch), for a depth_rtol that is negative or NaN, and when there is nothing
+ * to write.  The query returns 0 for every shape that the entry point refuses.
+ * hipGraph-capturable, no host synchronisation.  */
+int64_t g2v_cloud_consistency_workspace(int N, int H, int W);
+int g2v_cloud_consistency(const void* points, const void* local, const void* mask, const void* poses, const void* K,
+                          int N, int H, int W, float depth_rtol, int min_agree, int max_in_front,
+                          void* agree, void* in_front, void* pairs, void* mask_out,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- voxel-grid downsampling of the cloud (csrc/voxel.hip) ------------------------------------------------------------------
  * One vertex per occupied cell of the grid origin + k * voxel_size: the mean of the cell's points and of their colour bytes.
  * points fp32 [N,H,W,3], colors fp32 [N,3,H,W], mask u8 [N,H,W].  A pixel takes part if mask != 0 and its three coordinates are

@@ -3,7 +3,8 @@ Fixes the reference's Namespace-as-path bug and sorts the folder listing (SURVEY
 
 Flags of this project's own, all off by default (without them main() does what the reference's does): --conf-threshold,
 --edge-rtol, --edge-atol write the PLY through save_point_cloud's device filters; --intrinsics fits and prints a pinhole
-matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cloud on the device before it is written."""
+matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cloud on the device before it is written;
+--min-views, --max-in-front (with --consistency-rtol) add the multi-view consistency filter (point_cloud_mask)."""
 import argparse
 import os
 import sys
@@ -24,6 +25,11 @@ parser.add_argument("--intrinsics", action="store_true", help="fit, print and re
 parser.add_argument("--voxel-size", type=float, default=None, metavar="V",
                     help="voxel-downsample the cloud on the device: one vertex per occupied cell of a grid of spacing V")
 parser.add_argument("--voxel-min-points", type=int, default=1, metavar="K", help="with --voxel-size: drop cells with fewer than K points")
+parser.add_argument("--min-views", type=int, default=None, metavar="K",
+                    help="keep a point only if at least K other views confirm it (its depth there agrees within --consistency-rtol)")
+parser.add_argument("--max-in-front", type=int, default=None, metavar="M",
+                    help="keep a point only if at most M other views see it floating in front of their surface")
+parser.add_argument("--consistency-rtol", type=float, default=0.03, metavar="R", help="with --min-views / --max-in-front: the relative depth tolerance")
 
 
 def main(argv=None):
@@ -34,7 +40,12 @@ def main(argv=None):
     model, tokenizer, new_token_ids, vit_image_transform, dino_transform = load_model_and_tokenizer(args.model_path)
     pred = model.recon(tokenizer, new_token_ids, dino_transform, image_names)
     filtered = args.conf_threshold is not None or args.edge_rtol is not None or args.edge_atol is not None
-    if filtered or args.voxel_size is not None:
+    if args.min_views is not None or args.max_in_front is not None:
+        from g2vlm_utils import point_cloud_mask, save_point_cloud_masked
+        mask = point_cloud_mask(pred, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol,
+                                min_views=args.min_views, max_in_front=args.max_in_front, depth_rtol=args.consistency_rtol)
+        save_point_cloud_masked(pred, args.save_path, mask, voxel_size=args.voxel_size, min_points=args.voxel_min_points)
+    elif filtered or args.voxel_size is not None:
         from g2vlm_utils import save_point_cloud
         save_point_cloud(pred, args.save_path, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol,
                          voxel_size=args.voxel_size, min_points=args.voxel_min_points)
