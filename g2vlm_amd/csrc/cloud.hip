@@ -14,6 +14,7 @@
 // stream (4 pixels = 3 vectors) wherever the address allows, and the components are picked out of the vectors.
 #include <float.h>
 
+#include "cloud_colour.h"                                   // cc_colour: the colour byte of a record, shared with render.hip
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -196,11 +197,6 @@ __global__ __launch_bounds__(CC_THREADS) void cloud_scan_kernel(const int* block
     for (int j = 0; j < bpv; ++j) s += block_cnt[(long)n * bpv + j];
     counts[n] = s;
   }
-}
-
-__device__ __forceinline__ uint8_t cc_colour(float c) {      // host.write_ply_binary: (uint8)(clip((double)c, 0, 1) * 255)
-  const double v = fmin(fmax((double)c, 0.0), 1.0) * 255.0;
-  return (uint8_t)(int)v;
 }
 
 // grid (blocks per view, N).  The workgroup's records are staged in LDS at the byte offset its output range has inside a dword,

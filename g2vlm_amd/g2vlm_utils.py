@@ -439,3 +439,188 @@ def estimate_intrinsics(pred_dict, mask=None):
         mask = mask.contiguous()
     K, _ = hip.intrinsics_lsq(local, mask)
     return K.unsqueeze(0)
+
+
+# ---- rendering the cloud from any camera (csrc/render.hip) -------------------------------------------------------------------
+def _is_int(x):
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+
+def _render_args(splat_radius, background, size, default_size):
+    """(radius, 0xRRGGBB, (OH, OW)), or ValueError: before any launch"""
+    if not (_is_int(splat_radius) and 0 <= splat_radius <= 8):
+        raise ValueError(f"splat_radius must be an integer in [0, 8], got {splat_radius!r}")
+    try:
+        bg = list(background)
+    except TypeError:
+        bg = None
+    if bg is None or len(bg) != 3 or not all(_is_int(b) and 0 <= b <= 255 for b in bg):
+        raise ValueError(f"background must be three integers in [0, 255], got {background!r}")
+    if size is None:
+        size = default_size
+    try:
+        size = list(size)
+    except TypeError:
+        size = []
+    if len(size) != 2 or not all(_is_int(s) and s > 0 for s in size):
+        raise ValueError(f"size must be two positive integers (OH, OW), got {size!r}")
+    return int(splat_radius), (int(bg[0]) << 16) | (int(bg[1]) << 8) | int(bg[2]), (int(size[0]), int(size[1]))
+
+
+def _render_cameras(pred_dict, camera_poses, intrinsics, n):
+    """(poses fp32 [M,4,4] on the host's or the device's side as given, K fp32 [M,3,3] or None = estimate), or ValueError"""
+    if camera_poses is None:
+        poses = pred_dict.get("camera_poses")
+        if not torch.is_tensor(poses) or tuple(poses.shape) != (1, n, 4, 4):
+            raise ValueError(f"camera_poses=None takes pred_dict['camera_poses'] [1,N,4,4] with N = {n}, got "
+                             f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    else:
+        poses = camera_poses
+        if intrinsics is None:
+            raise ValueError("explicit camera_poses need intrinsics ([3,3] or [M,3,3]): for the scene's own cameras pass "
+                             "estimate_intrinsics(pred)[0, i]")
+    ok = torch.is_tensor(poses) and poses.is_floating_point() and poses.dim() in (3, 4) and tuple(poses.shape[-2:]) == (4, 4) and \
+        (poses.dim() == 3 or poses.shape[0] == 1) and poses.shape[-3] >= 1
+    if not ok:
+        raise ValueError(f"camera_poses: a floating-point tensor [M,4,4] or [1,M,4,4] expected, got "
+                         f"{(poses.dtype, tuple(poses.shape)) if torch.is_tensor(poses) else type(poses).__name__}")
+    poses = poses.detach().reshape(-1, 4, 4)
+    m = poses.shape[0]
+    if m > 65535:
+        raise ValueError(f"at most 65535 target cameras per call, got {m}")
+    if intrinsics is None:
+        return poses, None
+    K = intrinsics
+    if not (torch.is_tensor(K) and K.is_floating_point() and tuple(K.shape) in ((3, 3), (m, 3, 3), (1, m, 3, 3))):
+        raise ValueError(f"intrinsics: a floating-point tensor [3,3], [M,3,3] or [1,M,3,3] with M = {m} expected, got "
+                         f"{(K.dtype, tuple(K.shape)) if torch.is_tensor(K) else type(K).__name__}")
+    K = K.detach().float()
+    return poses, (K.expand(m, 3, 3) if K.dim() == 2 else K.reshape(m, 3, 3))
+
+
+def _render_skip(exclude_view, m, n):
+    """the source view left out of every target as m ints, or None"""
+    if exclude_view is None:
+        return None
+    if isinstance(exclude_view, str):
+        if exclude_view != "self":
+            raise ValueError(f"exclude_view: None, 'self' or {m} integers expected, got {exclude_view!r}")
+        if m != n:
+            raise ValueError(f"exclude_view='self' needs as many target cameras as source views, got {m} and {n}")
+        return list(range(n))
+    try:
+        skip = exclude_view.tolist() if hasattr(exclude_view, "tolist") else list(exclude_view)
+    except TypeError:
+        skip = None
+    if skip is None or len(skip) != m or not all(_is_int(s) and -2 ** 31 <= s < 2 ** 31 for s in skip):
+        raise ValueError(f"exclude_view: None, 'self' or {m} integers expected, got {exclude_view!r}")
+    return [int(s) for s in skip]
+
+
+def render_point_cloud(pred_dict, camera_poses=None, intrinsics=None, size=None, splat_radius=0, exclude_view=None,
+                       background=(0, 0, 0), mask=None, conf_threshold=None, edge_rtol=None, edge_atol=None, filter_nan=True):
+    """The cloud of a recon result seen from any camera, on the device (hip.cloud_render; include/g2vlm_hip.h and DESIGN.md 6l
+    have the exact rule): every kept pixel's world point is projected into every target camera, drawn as a square of
+    2 splat_radius + 1 pixels, and every target pixel keeps the nearest point that covers it (a z-buffer; equal depths go to the
+    lower source pixel).  One source pixel per target pixel, no blending: `index` says which.
+    The source pixels are those point_cloud_mask keeps under the same filter arguments; an explicit mask (bool / uint8 [N,H,W],
+    e.g. point_cloud_mask(min_views=...)'s) replaces the filters.
+    camera_poses: [M,4,4] or [1,M,4,4] camera-to-world; None takes the scene's own pred_dict["camera_poses"] (M = N).
+    intrinsics: [3,3] (one K for every target), [M,3,3] or [1,M,3,3], used as given (never rescaled to `size`); None is allowed
+    only with camera_poses=None and takes estimate_intrinsics over the same mask.  size = (OH, OW), default (H, W).
+    exclude_view: None, "self" (target m leaves out source view m: leave-one-out re-rendering, needs M == N) or M integers (the
+    source view each target leaves out; -1 for none).  background: (r, g, b) bytes for the pixels nothing covers.
+    Returns, on the device, dict(color uint8 [M,OH,OW,3] - the bytes the PLY export writes for the source pixel -, depth fp32
+    [M,OH,OW] (0 where nothing lands), index int32 [M,OH,OW] = the flat source pixel (i H + y) W + x or -1, intrinsics fp32
+    [M,3,3]).  ValueError for every bad argument, before any launch."""
+    from . import hip
+    if mask is not None:
+        points, local, _, images, _ = _cloud_inputs(pred_dict, None, None, None, need_images=True)
+        conf = logit = None
+    else:
+        points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=True)
+    n, h, w = points.shape[:3]
+    radius, bg, (oh, ow) = _render_args(splat_radius, background, size, (h, w))
+    poses, K = _render_cameras(pred_dict, camera_poses, intrinsics, n)
+    m = poses.shape[0]
+    if m * oh * ow > 2 ** 31 - 1:
+        raise ValueError(f"{m} targets of {oh} x {ow} are more than 2^31 - 1 pixels: render fewer cameras per call")
+    skip = _render_skip(exclude_view, m, n)
+    if mask is not None:
+        base = _voxel_mask(mask, points.shape[:3], points.device)
+    else:
+        base = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    if K is None:
+        K, _ = hip.intrinsics_lsq(local, base)
+    dev = points.device
+    K = K.to(dev).contiguous()
+    poses = poses.to(dev).float().contiguous()
+    if skip is not None:
+        skip = torch.tensor(skip, dtype=torch.int32).to(dev)
+    color, depth, index = hip.cloud_render(points, images, base, poses, K, (oh, ow), radius, bg, skip)
+    return dict(color=color, depth=depth, index=index, intrinsics=K)
+
+
+def orbit_poses(pred_dict, frames=36, mask=None):
+    """A turntable through the scene's own cameras: fp32 [frames,4,4] camera-to-world (a host tensor; fp64 arithmetic on the
+    host, rounded once).  Centre c = the per-axis median of the kept finite world points (mask: bool / uint8 [N,H,W], None = all);
+    up = the normalised mean of the cameras' negated y axes (column 1 of a pose points down); height h = the mean of
+    (centre_i - c) . up and radius rho = the mean norm of the part of (centre_i - c) perpendicular to up.  Frame k stands at
+    c + h up + rho (cos a e1 + sin a e2), a = 2 pi k / frames, e1 = the normalised perpendicular part of camera 0's offset - frame 0
+    has camera 0's azimuth -, e2 = up x e1, and looks at c: the rotation's columns are right = forward x up (normalised), down =
+    forward x right, forward.  ValueError if no point is kept or up or the orbit is degenerate."""
+    if not (_is_int(frames) and frames >= 1):
+        raise ValueError(f"frames must be an integer >= 1, got {frames!r}")
+    points = pred_dict["points"]
+    if points.dim() != 5 or points.shape[0] != 1 or points.shape[-1] != 3:
+        raise ValueError(f"points [1,N,H,W,3] expected, got {tuple(points.shape)}")
+    n = points.shape[1]
+    poses = pred_dict.get("camera_poses")
+    if not torch.is_tensor(poses) or tuple(poses.shape) != (1, n, 4, 4):
+        raise ValueError(f"orbit_poses needs pred_dict['camera_poses'] [1,N,4,4] with N = {n}, got "
+                         f"{tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+    p = points[0].detach().double().cpu().numpy()
+    keep = np.isfinite(p).all(-1)
+    if mask is not None:
+        keep &= _voxel_mask(mask, points.shape[1:4], "cpu").numpy() != 0
+    if not keep.any():
+        raise ValueError("orbit_poses: no finite point is kept")
+    c = np.median(p[keep], axis=0)
+    cam = poses[0].detach().double().cpu().numpy()
+    up = -cam[:, :3, 1].mean(0)
+    norm = np.linalg.norm(up)
+    if not (np.isfinite(norm) and norm > 1e-9):
+        raise ValueError("orbit_poses: the cameras' up directions cancel (or are not finite): no turntable axis")
+    up = up / norm
+    off = cam[:, :3, 3] - c
+    along = off @ up
+    perp = off - along[:, None] * up
+    h, rho = along.mean(), np.linalg.norm(perp, axis=1).mean()
+    e1n = np.linalg.norm(perp[0])
+    if not (np.isfinite(e1n) and e1n > 1e-9 and np.isfinite(h) and rho > 1e-9):
+        raise ValueError("orbit_poses: camera 0 stands on the turntable's axis (or a pose is not finite): no azimuth to start from")
+    e1 = perp[0] / e1n
+    e2 = np.cross(up, e1)
+    out = np.zeros((frames, 4, 4))
+    for k in range(frames):
+        a = 2.0 * np.pi * k / frames
+        pos = c + h * up + rho * (np.cos(a) * e1 + np.sin(a) * e2)
+        fwd = (c - pos) / np.linalg.norm(c - pos)
+        right = np.cross(fwd, up)
+        right /= np.linalg.norm(right)                       # rho > 0: forward is never parallel to up
+        out[k, :3, 0], out[k, :3, 1], out[k, :3, 2], out[k, :3, 3], out[k, 3, 3] = right, np.cross(fwd, right), fwd, pos, 1.0
+    return torch.from_numpy(out.astype(np.float32))
+
+
+def save_rendered_views(render, directory, prefix="view"):
+    """render_point_cloud's colour images as PNGs directory/prefix_000.png ... (Pillow); returns the paths"""
+    from PIL import Image
+    color = render["color"]
+    if not torch.is_tensor(color) or color.dtype != torch.uint8 or color.dim() != 4 or color.shape[-1] != 3:
+        raise ValueError("render['color']: uint8 [M,OH,OW,3] expected (render_point_cloud's result)")
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for k, img in enumerate(color.cpu().numpy()):
+        paths.append(os.path.join(directory, f"{prefix}_{k:03d}.png"))
+        Image.fromarray(img).save(paths[-1])
+    return paths

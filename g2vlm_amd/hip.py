@@ -110,6 +110,8 @@ _SIGS = {
     "g2v_intrinsics_lsq": ([_P, _P, _I, _I, _I, _P, _P, _P, _L, _P], C.c_int),
     "g2v_cloud_consistency_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_cloud_consistency": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_render_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_cloud_render": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
@@ -1072,6 +1074,46 @@ def cloud_consistency(points, local, mask, poses, K, depth_rtol, min_agree=0, ma
                                     int(max_in_front), _p(agree), _p(in_front), _p(pair_counts), _p(mask_out), _p(workspace),
                                     workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_consistency")
     return agree, in_front, mask_out, pair_counts
+
+
+# ------------------------------------------------------------------------------------------ z-buffer rendering (csrc/render.hip)
+def cloud_render_workspace(M, OH, OW):
+    return int(lib().g2v_cloud_render_workspace(int(M), int(OH), int(OW)))
+
+
+def cloud_render(points, colors, mask, poses, K, size, radius=0, background=0, skip=None, color=True, depth=True, index=True,
+                 workspace=None):
+    """The cloud seen from M target cameras through a z-buffer (g2v_cloud_render; include/g2vlm_hip.h has the exact rule): points
+    fp32 [N,H,W,3], colors fp32 [N,3,H,W] (None only with color=False), mask uint8 or bool [N,H,W] or None (all pixels), poses
+    fp32 [M,4,4] camera-to-world and K fp32 [M,3,3] of the targets, size = (OH, OW), radius 0..8 = the half-width of a point's
+    square, background 0xRRGGBB, skip int32 [M] or None = the source view left out of each target.  Returns (color uint8
+    [M,OH,OW,3], depth fp32 [M,OH,OW], index int32 [M,OH,OW] = the flat source pixel or -1), None for an output switched off.
+    Bit-reproducible; no host synchronisation."""
+    N, H, W = _nhw3(points, "points")
+    if colors is not None:
+        assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
+            "colors: fp32 [N,3,H,W], contiguous"
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    assert poses.dim() == 3, "poses: fp32 [M,4,4]"
+    M, (OH, OW) = poses.shape[0], size
+    for t, shape, what in ((poses, (M, 4, 4), "poses"), (K, (M, 3, 3), "K")):
+        assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous(), f"{what}: fp32 {list(shape)}, contiguous"
+    if skip is not None:
+        assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (M,) and skip.is_contiguous(), "skip: int32 [M]"
+    dev = points.device
+    nbytes = cloud_render_workspace(M, OH, OW)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, dev, "render")
+    color_out = torch.empty((M, OH, OW, 3), dtype=torch.uint8, device=dev) if color else None
+    depth_out = torch.empty((M, OH, OW), dtype=torch.float32, device=dev) if depth else None
+    index_out = torch.empty((M, OH, OW), dtype=torch.int32, device=dev) if index else None
+    _ck(lib().g2v_cloud_render(_p(points), _p(colors), _p(mask), N, H, W, _p(poses), _p(K), _p(skip), M, int(OH), int(OW), int(radius),
+                               int(background), _p(color_out), _p(depth_out), _p(index_out), _p(workspace),
+                               workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_render")
+    return color_out, depth_out, index_out
 
 
 # ------------------------------------------------------------------------------------------ voxel downsampling (csrc/voxel.hip)

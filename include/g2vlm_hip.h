@@ -466,6 +466,42 @@ int g2v_cloud_consistency(const void* points, const void* local, const void* mas
                           void* agree, void* in_front, void* pairs, void* mask_out,
                           void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- rendering the cloud from any camera with a z-buffer (csrc/render.hip) ----------------------------------------------------
+ * points fp32 [N,H,W,3] (world), colors fp32 [N,3,H,W] (may be NULL only when color_out is NULL), mask u8 [N,H,W] or NULL (all
+ * pixels): the SOURCE, as above.  poses fp32 [M,4,4] camera-to-world and K fp32 [M,3,3] of the M TARGET cameras (R, t, fx, fy,
+ * cx, cy as in the consistency section), target images of OH x OW pixels.  skip int32 [M] or NULL: source view skip[m] takes no
+ * part in target m; -1 or any value outside [0, N) leaves nobody out.  radius 0..8: the half-width of the square a point is
+ * drawn as.  background: 0xRRGGBB.
+ *
+ * The rule is exact: fp32 throughout, every operation rounded once, no fused multiply-add, every comparison an IEEE compare
+ * (false on NaN).  For target m and the source pixel with flat index p = (i H + y) W + x and world point P:
+ *   eligible iff mask[p] != 0, the three coordinates of P are finite and i != skip[m];
+ *   d = P - t;  q_k = (R[0][k] d0 + R[1][k] d1) + R[2][k] d2  (k = 0, 1, 2: R^T d, parenthesised as written);
+ *   u = fx (q0 / q2) + cx,  v = fy (q1 / q2) + cy, the divisions correctly rounded;
+ *   the point lands iff q2 > 0, q2 is finite, u >= 0 && u < OW and v >= 0 && v < OH; only then x0 = (int)u, y0 = (int)v (the
+ *   centre must be inside the image), and the point covers the pixels [x0 - radius, x0 + radius] x [y0 - radius, y0 + radius]
+ *   clipped to the image;
+ *   its key is ((uint64)bits(q2) << 32) | (uint32)p.  A target pixel keeps the MINIMUM key over the points that cover it: for
+ *   positive finite floats bit order is value order, so the nearest point wins and the lower source index among equal depths.
+ *   Keys are distinct and the minimum is associative: the result does not depend on the order in which anything ran.
+ * Resolve: a pixel that no point covers gets background, depth 0.0f and index -1; otherwise depth = the float in the key's high
+ * word, index = its low word, and colour = the three bytes the PLY export writes for source pixel index:
+ * (uint8)(clip((double)c, 0, 1) * 255) of colors[i, 0..2, y, x].
+ *
+ * Outputs, each optional (NULL) but not all three at once: color_out u8 [M,OH,OW,3], depth_out fp32 [M,OH,OW], index_out int32
+ * [M,OH,OW].  The workspace (8 M OH OW bytes, 8-byte aligned, no initialisation needed) holds the keys; the entry point fills
+ * it itself.  -22 before any launch for a dimension <= 0, N H W or M OH OW above 2^31 - 1, M > 65535, a radius outside [0, 8], a
+ * background outside [0, 0xFFFFFF], a required pointer that is NULL, an fp32 / int32 pointer that is not 4-byte aligned, a
+ * workspace that is too small or not 8-byte aligned, colors NULL with color_out given, and when there is nothing to write.
+ * The query returns 0 for every target shape that the entry point refuses.
+ * Three launches (fill, splat, resolve) on the stream; hipGraph-capturable, no host synchronisation.  */
+int64_t g2v_cloud_render_workspace(int M, int OH, int OW);
+int g2v_cloud_render(const void* points, const void* colors, const void* mask, int N, int H, int W,
+                     const void* poses, const void* K, const void* skip, int M, int OH, int OW,
+                     int radius, int background,
+                     void* color_out, void* depth_out, void* index_out,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- voxel-grid downsampling of the cloud (csrc/voxel.hip) ------------------------------------------------------------------
  * One vertex per occupied cell of the grid origin + k * voxel_size: the mean of the cell's points and of their colour bytes.
  * points fp32 [N,H,W,3], colors fp32 [N,3,H,W], mask u8 [N,H,W].  A pixel takes part if mask != 0 and its three coordinates are

@@ -4,7 +4,9 @@ Fixes the reference's Namespace-as-path bug and sorts the folder listing (SURVEY
 Flags of this project's own, all off by default (without them main() does what the reference's does): --conf-threshold,
 --edge-rtol, --edge-atol write the PLY through save_point_cloud's device filters; --intrinsics fits and prints a pinhole
 matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cloud on the device before it is written;
---min-views, --max-in-front (with --consistency-rtol) add the multi-view consistency filter (point_cloud_mask)."""
+--min-views, --max-in-front (with --consistency-rtol) add the multi-view consistency filter (point_cloud_mask);
+--render-dir writes one PNG per input view, re-rendered from the OTHER views' points (render_point_cloud, under the filters given),
+--render-orbit F adds F turntable frames there, --render-radius and --render-size set the splat half-width and the image size."""
 import argparse
 import os
 import sys
@@ -30,10 +32,38 @@ parser.add_argument("--min-views", type=int, default=None, metavar="K",
 parser.add_argument("--max-in-front", type=int, default=None, metavar="M",
                     help="keep a point only if at most M other views see it floating in front of their surface")
 parser.add_argument("--consistency-rtol", type=float, default=0.03, metavar="R", help="with --min-views / --max-in-front: the relative depth tolerance")
+parser.add_argument("--render-dir", type=str, default=None, metavar="DIR",
+                    help="write view_000.png ...: every input view re-rendered from the other views' points (leave-one-out)")
+parser.add_argument("--render-orbit", type=int, default=None, metavar="F",
+                    help="with --render-dir: also write orbit_000.png ..., F turntable frames through the scene's own cameras")
+parser.add_argument("--render-radius", type=int, default=1, metavar="R", help="with --render-dir: a point is drawn as a square of 2R+1 pixels (0..8)")
+parser.add_argument("--render-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --render-dir: the size of the rendered images")
+
+
+def render_views(pred, args):
+    """--render-dir / --render-orbit: the PNGs, under the filters given on the command line"""
+    from g2vlm_utils import estimate_intrinsics, orbit_poses, point_cloud_mask, render_point_cloud, save_rendered_views
+    consistency = {}
+    if args.min_views is not None or args.max_in_front is not None:
+        consistency = dict(min_views=args.min_views, max_in_front=args.max_in_front, depth_rtol=args.consistency_rtol)
+    mask = point_cloud_mask(pred, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol, **consistency)
+    size = None if args.render_size is None else tuple(args.render_size)
+    views = render_point_cloud(pred, size=size, splat_radius=args.render_radius, exclude_view="self", mask=mask)
+    paths = save_rendered_views(views, args.render_dir, prefix="view")
+    if args.render_orbit is not None:
+        K = estimate_intrinsics(pred, mask)[0, 0]
+        orbit = render_point_cloud(pred, camera_poses=orbit_poses(pred, args.render_orbit, mask=mask), intrinsics=K, size=size,
+                                   splat_radius=args.render_radius, mask=mask)
+        paths += save_rendered_views(orbit, args.render_dir, prefix="orbit")
+    print(f"{args.render_dir}: {len(paths)} rendered images")
 
 
 def main(argv=None):
     args = parser.parse_args(argv)
+    if args.render_orbit is not None and (args.render_dir is None or args.render_orbit < 1):
+        parser.error("--render-orbit F needs --render-dir and F >= 1")
+    if not 0 <= args.render_radius <= 8:
+        parser.error("--render-radius must be in 0..8")
     names = sorted(n for n in os.listdir(args.image_folder) if n.lower().endswith((".png", ".jpg", ".jpeg")))
     image_names = [os.path.join(args.image_folder, n) for n in names]
     print(image_names)
@@ -51,6 +81,8 @@ def main(argv=None):
                          voxel_size=args.voxel_size, min_points=args.voxel_min_points)
     else:
         save_ply_visualization(pred, args.save_path)
+    if args.render_dir is not None:
+        render_views(pred, args)
     if args.intrinsics:
         from g2vlm_utils import estimate_intrinsics
         # over every valid pixel: X/Z and Y/Z of a local point (xy z, z) do not depend on its depth, so the depth filters have
