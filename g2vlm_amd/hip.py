@@ -412,11 +412,15 @@ def make_attn_plan(windows, Hq, device, max_blocks=None, tile_rows=128, align_sh
     """windows: list of (q_start, q_len, k_start, k_len, causal[, phase]).  One descriptor per tile_rows-row query tile of
     every window.  Windows with the same query rows and disjoint KV ranges (the view-sharded prefill: local K/V block in
     phase 0, the other ranks' blocks in phase 1) are merged by the combine pass that follows the LAST phase; every phase is
-    its own launch (flash_attn(..., phase=i)), so a collective can run between them."""
+    its own launch (flash_attn(..., phase=i)), so a collective can run between them.
+    A causal window needs k_len >= q_len: the mask is bottom-right aligned, so with fewer keys than queries the first
+    q_len - k_len rows see no key at all (their output would be left unwritten, or 0 x 1/0 inside a mixed tile)."""
     rows, desc_nkt, desc_phase, out_tiles = [], [], [], {}
     for win in windows:
         qs, ql, ks, kl, causal = win[:5]
         ph = win[5] if len(win) > 5 else 0
+        if causal and kl < ql:
+            raise ValueError(f"causal attention window {tuple(win)}: k_len {kl} < q_len {ql} leaves {ql - kl} query rows without a key")
         shift = (kl - ql) if causal else NO_CAUSAL
         for t0 in range(0, ql, tile_rows):
             qr = min(tile_rows, ql - t0)

@@ -114,7 +114,10 @@ int g2v_qknorm_mrope_cache(const void* qkv, int L, int Hq, int Hkv,
 typedef struct {
   int32_t q0, q_rows;     /* query rows [q0, q0+q_rows) (<= tile_rows) of one window               */
   int32_t k0, k_len;      /* keys [k0, k0+k_len) of that window                                    */
-  int32_t causal_shift;   /* key j allowed iff j - k0 <= (q - q_win0) + shift; INT32_MAX/2 = none  */
+  int32_t causal_shift;   /* key j allowed iff j - k0 <= (q - q_win0) + shift; INT32_MAX/2 = none.
+                           * Every query row of a descriptor must be allowed at least one key (shift >= 0 for a
+                           * window's first row): the output of a row without a key is UNDEFINED here (NaN from
+                           * 0 x 1/0, or never written); make_attn_plan refuses causal windows with k_len < q_len. */
   int32_t q_win0;         /* first query row of the window                                         */
   int32_t _pad[2];
 } g2v_attn_tile;          /* device array, one entry per (window, 128-row query tile)              */

@@ -38,6 +38,9 @@ Forms (launch_flash picks the kernel from D, tile_rows = 32 x waves and ldk == l
     flash_fwd_kernel<128,8> 128  8      form 0 (g2v_debug_attn_form), padded strides, 12:2    test_edge_sweep[128-*]
     flash_fwd64_kernel      128  4x64   MoT C3, view-sharded C4 phases; q 1536 / cache 256     test_mot, test_c4_rank_phases, test_edge_sweep[128-*], test_fwd64_rescale_threshold
     flash_combine_kernel    all  -      every edge case again at max_blocks 3 and 7; C4 phases test_edge_sweep, test_c4_rank_phases
+Every row of this table runs again in tests/test_flash_profile_gpu.py on structured score profiles (one key or one tile carries
+the row, equal weights, +-250 offsets, steps of up to 200 per KV tile; max_blocks None / 3 / 7), every ELEMENT against fp64 under
+bounds derived from the kernels' arithmetic instead of measured on them (tests/flash_profile_check.py).
 
 Bounds.  Rule: every case is measured under its production form and under the 4-wave 128-row form on the same inputs;
 the bound of a head dim is 1.5 x the largest e_max / e_row measured for that D over all cases and forms on an MI355X.
@@ -61,16 +64,19 @@ The whole module runs in about 7 s on one MI355X.
 """
 import copy
 import math
+import os
+import sys
 
 import pytest
 import torch
 
-pytestmark = pytest.mark.gpu
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+# shared with tests/test_flash_profile_gpu.py and kept in its helper module: the fp64 reference, the guarded launch, the padded
+# inputs, the form table and the row bounds BOUND[D] (per head dim (e_max, e_row): the rule and the measured maxima are above)
+from flash_profile_check import (BOUND, GLOBAL_REL, K0, NAN_BITS, Q0, SWEEP_DS, attn_form, covered_rows, forms, heads,  # noqa: E402,F401
+                                 launch, nan_bf16, padded_inputs, ref_fp64)
 
-NAN_BITS = 0x7FA5                      # bf16 quiet NaN with a payload no kernel writes
-GLOBAL_REL = 6e-3
-# per head dim: (e_max, e_row) bounds - see the module docstring for the rule and the measured maxima
-BOUND = {16: (2.43e-2, 8.72e-3), 64: (2.87e-2, 5.44e-3), 80: (2.87e-2, 5.33e-3), 96: (2.72e-2, 5.11e-3), 128: (3.36e-2, 5.90e-3)}
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -79,19 +85,6 @@ def hip():
     h.lib()
     assert torch.cuda.is_available(), "these tests need the MI355X"
     return h
-
-
-class attn_form:
-    """g2v_debug_attn_form for the duration of a block (0 = flash_fwd_kernel<128,8> for 256-row items), restored to 1."""
-
-    def __init__(self, hip, f):
-        self.hip, self.f = hip, f
-
-    def __enter__(self):
-        self.hip.lib().g2v_debug_attn_form(self.f)
-
-    def __exit__(self, *exc):
-        self.hip.lib().g2v_debug_attn_form(1)
 
 
 def gen(seed):
@@ -104,45 +97,7 @@ def randn(g, *shape, scale=1.0):
     return torch.randn(shape, generator=g, device="cuda") * scale
 
 
-def nan_bf16(rows, cols):
-    return torch.full((rows, cols), float("nan"), dtype=torch.bfloat16, device="cuda")
-
-
 # ------------------------------------------------------------------------------------------------ reference and metric
-def ref_fp64(q, k, v, windows, Hq, Hkv, D, scale=None):
-    """Attention of the bf16 views q [*, >= Hq*D], k / v [*, >= Hkv*D] in float64: per window softmax(Q K^T scale) V,
-    GQA by head repeat, bottom-right causal mask.  Windows with the same query rows are ONE softmax over the union of
-    their key ranges (the phases of a view-sharded plan).  Returns {(q0, q_len): float64 [q_len, Hq, D]}."""
-    scale = D ** -0.5 if scale is None else scale
-    rep = Hq // Hkv
-    groups = {}
-    for w in windows:
-        groups.setdefault((w[0], w[1]), []).append(w)
-    out = {}
-    for (q0, ql), ws in groups.items():
-        causal = bool(ws[0][4])
-        assert len(ws) == 1 or not causal
-        rows = torch.cat([torch.arange(w[2], w[2] + w[3], device=q.device) for w in ws])
-        K = k[rows, :Hkv * D].view(-1, Hkv, D).double()
-        V = v[rows, :Hkv * D].view(-1, Hkv, D).double()
-        Lk = K.shape[0]
-        o = torch.empty((ql, Hq, D), dtype=torch.float64, device=q.device)
-        blk = max(1, min(ql, (1 << 25) // (rep * Lk)))
-        for h in range(Hkv):
-            Kt, Vh = K[:, h].t(), V[:, h]
-            for r0 in range(0, ql, blk):
-                r1 = min(ql, r0 + blk)
-                Q = q[q0 + r0:q0 + r1, h * rep * D:(h + 1) * rep * D].double().view(r1 - r0, rep, D).transpose(0, 1)
-                s = torch.matmul(Q, Kt) * scale
-                if causal:
-                    i = torch.arange(r0, r1, device=q.device).view(-1, 1)
-                    j = torch.arange(Lk, device=q.device).view(1, -1)
-                    s.masked_fill_(j > i + (Lk - ql), float("-inf"))
-                o[r0:r1, h * rep:(h + 1) * rep] = torch.matmul(torch.softmax(s, dim=-1), Vh).transpose(0, 1)
-        out[(q0, ql)] = o
-    return out
-
-
 class Errors:
     """Row metric of one launch: e_max / e_row per (row, head) of every window, and the global rel-L2."""
 
@@ -164,30 +119,6 @@ class Errors:
     def flagged(self, D):
         bm, br = BOUND[D]
         return {q0: (self.e_max[q0] > bm) | (self.e_row[q0] > br) for q0 in self.e_max}
-
-
-def covered_rows(windows, n_rows):
-    m = torch.zeros(n_rows, dtype=torch.bool, device="cuda")
-    for w in windows:
-        m[w[0]:w[0] + w[1]] = True
-    return m
-
-
-def launch(hip, q, k, v, plan, Hq, Hkv, D, windows, n_rows, ldo, phase_by_phase=False):
-    """One attention into a NaN-payload output [n_rows, ldo]; checks that the kernel wrote exactly the window rows x [0, Hq*D)
-    and left every other bit alone.  Returns the output view [n_rows, Hq*D]."""
-    buf = torch.full((n_rows, ldo), NAN_BITS, dtype=torch.int16, device="cuda")
-    out = buf.view(torch.bfloat16)[:, :Hq * D]
-    if phase_by_phase:
-        for ph in range(len(plan.phases)):
-            hip.flash_attn(q, k, v, out, plan, Hq, Hkv, D, phase=ph)
-    else:
-        hip.flash_attn(q, k, v, out, plan, Hq, Hkv, D)
-    cov = covered_rows(windows, n_rows)
-    assert bool((buf[~cov] == NAN_BITS).all()), "a row outside every window was written"
-    assert bool((buf[:, Hq * D:] == NAN_BITS).all()), "a column past Hq*D was written"
-    assert bool(torch.isfinite(out[cov].float()).all()), "non-finite output inside a window (read outside the window?)"
-    return out
 
 
 def same_bits(a, b):
@@ -221,26 +152,6 @@ def test_fp64_reference_matches_oracle():
 
 
 # ------------------------------------------------------------------------------------------------ edge sweeps (section 3)
-Q0, K0 = 5, 7                                 # the window starts inside the buffers: rows before it are NaN
-
-
-def padded_inputs(Lq, Lk, Hq, Hkv, D, q_val, k_val, v_val):
-    """Window [Q0, Q0+Lq) of q and [K0, K0+Lk) of k / v in NaN-filled buffers with strides wider than H*D."""
-    ldq, ldk = Hq * D + 24, Hkv * D + 40
-    q, k, v = nan_bf16(Q0 + Lq + 3, ldq), nan_bf16(K0 + Lk + 4, ldk), nan_bf16(K0 + Lk + 4, ldk)
-    q[Q0:Q0 + Lq, :Hq * D] = q_val.reshape(Lq, Hq * D).bfloat16()
-    k[K0:K0 + Lk, :Hkv * D] = k_val.reshape(Lk, Hkv * D).bfloat16()
-    v[K0:K0 + Lk, :Hkv * D] = v_val.reshape(Lk, Hkv * D).bfloat16()
-    return q[:, :Hq * D], k[:, :Hkv * D], v[:, :Hkv * D]
-
-
-def forms(D):
-    """(name, tile_rows, g2v_debug_attn_form): the 4-wave form first (the yardstick), then the 8-wave ones."""
-    if D == 128:
-        return [("4w", 128, 1), ("8w", 256, 0), ("fwd64", 256, 1)]
-    return [("4w", 128, 1), ("8w", 256, 1)]
-
-
 def run_forms(hip, q, k, v, wins, Hq, Hkv, D, what, max_blocks_list=(None, 3, 7)):
     """Every form of D x every max_blocks on one input; row bounds on each, and each 8-wave form against the 4-wave form."""
     ref = ref_fp64(q, k, v, wins, Hq, Hkv, D)
@@ -257,11 +168,6 @@ def run_forms(hip, q, k, v, wins, Hq, Hkv, D, what, max_blocks_list=(None, 3, 7)
             check_vs_4wave(errs[name], errs["4w"], f"{what} {name} mb={mb}")
 
 
-def heads(D):
-    return (12, 2) if D == 128 else (4, 4)
-
-
-SWEEP_DS = [16, 64, 80, 96, 128]
 LK_SWEEP = [1, 2, 63, 64, 65, 127, 128, 129, 357]
 LQ_SWEEP = [1, 31, 32, 33, 63, 65, 127, 128, 129, 255, 256, 257, 2 * 128 + 37, 2 * 256 + 37]
 CAUSAL_SWEEP = [(1, 1), (33, 33), (65, 65), (129, 129), (257, 257), (100, 164), (257, 300), (37, 1000)]
