@@ -441,6 +441,73 @@ def estimate_intrinsics(pred_dict, mask=None):
     return K.unsqueeze(0)
 
 
+# ---- triangle-mesh export (csrc/mesh.hip) ------------------------------------------------------------------------------------
+def _mesh_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, filter_nan, min_views, max_in_front, depth_rtol, intrinsics, mask,
+                 max_edge):
+    """(points [N,H,W,3], images [N,3,H,W], mask uint8 [N,H,W], max_edge as a float or None) on the device, or ValueError: every
+    check comes before any launch"""
+    if max_edge is not None:
+        try:
+            ok = not isinstance(max_edge, bool) and float(max_edge) >= 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"max_edge must be a number >= 0 (or None: no limit), got {max_edge!r}")
+        max_edge = float(max_edge)
+    if mask is not None:
+        given = [k for k, v, d in (("conf_threshold", conf_threshold, None), ("edge_rtol", edge_rtol, 0.03), ("edge_atol", edge_atol, None),
+                                   ("filter_nan", filter_nan, True), ("min_views", min_views, None), ("max_in_front", max_in_front, None),
+                                   ("depth_rtol", depth_rtol, 0.03), ("intrinsics", intrinsics, None)) if not (v is d or v == d)]
+        if given:
+            raise ValueError(f"an explicit mask replaces the filters: {', '.join(given)} may not be given with it")
+    points, _, _, images, _ = _cloud_inputs(pred_dict, None, None, None, need_images=True)
+    n, h, w = points.shape[:3]
+    if n > 65535 or 2 * n * (h - 1) * (w - 1) > 2 ** 31 - 1:
+        raise ValueError(f"{n} views of {h} x {w} are more than a mesh holds (65535 views, 2^31 - 1 candidate triangles)")
+    if mask is not None:
+        return points, images, _voxel_mask(mask, points.shape[:3], points.device), max_edge
+    keep = point_cloud_mask(pred_dict, conf_threshold, edge_rtol, edge_atol, filter_nan, min_views, max_in_front, depth_rtol, intrinsics)
+    return points, images, keep.view(torch.uint8), max_edge
+
+
+def reconstruct_mesh(pred_dict, conf_threshold=None, edge_rtol=0.03, edge_atol=None, filter_nan=True, min_views=None,
+                     max_in_front=None, depth_rtol=0.03, intrinsics=None, mask=None, max_edge=None):
+    """The reconstruction as a triangle mesh, on the device (hip.cloud_mesh; include/g2vlm_hip.h and DESIGN.md 6n have the exact
+    rule): every view's pixel grid is triangulated - a quad whose four corners are kept is cut along its shorter diagonal, a quad
+    with three kept corners gives one triangle - and the triangles face the camera that saw them.  The views stay separate sheets.
+    The kept pixels are those of point_cloud_mask under the same filter arguments (edge_rtol = 0.03 by default: no triangle spans a
+    depth discontinuity); an explicit mask (bool / uint8 [N,H,W], e.g. point_cloud_mask(...)'s) replaces the filters and may not be
+    combined with them.  max_edge: triangles with an edge longer than this (in the units of the points) are dropped as well.
+    Returns dict(vertices fp32 [V,3], colors uint8 [V,3] - the bytes the PLY export writes -, faces int32 [F,3] of vertex ids,
+    vertex_pixel int32 [V] = the flat pixel (i H + y) W + x of every vertex, increasing, counts int32 [N,2] = vertices and faces
+    per view).  Only pixels that a face references are vertices.  ValueError for every bad argument, before any launch."""
+    from . import hip
+    points, images, keep, max_edge = _mesh_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, filter_nan, min_views, max_in_front,
+                                                  depth_rtol, intrinsics, mask, max_edge)
+    m = hip.cloud_mesh(points, images, keep, max_edge, face_records=False)
+    rec = m["vertex_records"]
+    return dict(vertices=rec[:, :12].reshape(-1).view(torch.float32).view(-1, 3), colors=rec[:, 12:].contiguous(), faces=m["faces"],
+                vertex_pixel=torch.nonzero(m["used"].reshape(-1)).reshape(-1).to(torch.int32), counts=m["counts"])
+
+
+def save_mesh(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_atol=None, filter_nan=True, min_views=None,
+              max_in_front=None, depth_rtol=0.03, intrinsics=None, mask=None, max_edge=None, verbose=True):
+    """reconstruct_mesh's mesh as a binary little-endian PLY that mesh viewers open: the vertex block of save_point_cloud_masked
+    for the used pixels, then `element face F` / `property list uchar int vertex_indices`.  Both blocks are packed on the device:
+    one device-to-host copy each, one write.  Returns dict(num_vertices, num_faces, counts = [vertices, faces] per view)."""
+    from . import hip
+    points, images, keep, max_edge = _mesh_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, filter_nan, min_views, max_in_front,
+                                                  depth_rtol, intrinsics, mask, max_edge)
+    m = hip.cloud_mesh(points, images, keep, max_edge, faces=False)
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    host.write_ply_mesh(save_path, m["vertex_records"].cpu(), m["face_records"].cpu())
+    counts = m["counts"].cpu().tolist()
+    nv, nf = int(m["vertex_records"].shape[0]), int(m["face_records"].shape[0])
+    if verbose:
+        print(f"{save_path}: {nv} vertices of {keep.numel()} pixels, {nf} triangles, per view {counts}")
+    return dict(num_vertices=nv, num_faces=nf, counts=counts)
+
+
 # ---- rendering the cloud from any camera (csrc/render.hip) -------------------------------------------------------------------
 def _is_int(x):
     return not isinstance(x, bool) and isinstance(x, (int, np.integer))

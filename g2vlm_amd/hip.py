@@ -112,6 +112,8 @@ _SIGS = {
     "g2v_cloud_consistency": ([_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_cloud_render_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_cloud_render": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_mesh_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_cloud_mesh": ([_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P, _P, _L, _P], C.c_int),
     "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
@@ -1120,8 +1122,70 @@ def cloud_render(points, colors, mask, poses, K, size, radius=0, background=0, s
     return color_out, depth_out, index_out
 
 
+# ------------------------------------------------------------------------------------------ triangle-mesh export (csrc/mesh.hip)
+MESH_MAX_EDGE = 1                                           # G2V_MESH_MAX_EDGE
+
+
+def cloud_mesh_workspace(N, H, W):
+    return int(lib().g2v_cloud_mesh_workspace(int(N), int(H), int(W)))
+
+
+def cloud_mesh_raw(points, mask, max_edge, counts, used=None, vertex_of=None, faces=None, face_records=None, workspace=None):
+    """One call of g2v_cloud_mesh into the caller's tensors (no allocation but a grown workspace, no host synchronisation):
+    counts int32 [N,2] always; used uint8 [N,H,W], vertex_of int32 [N,H,W], faces int32 [cap,3], face_records uint8 [cap,13] where
+    given - the capacity is that of the face tensors (0 without them: the call then only counts)."""
+    N, H, W = _nhw3(points, "points")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    assert counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (N, 2) and counts.is_contiguous(), "counts: int32 [N,2]"
+    for t, dtype, what in ((used, torch.uint8, "used"), (vertex_of, torch.int32, "vertex_of")):
+        assert t is None or (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (N, H, W) and t.is_contiguous()), f"{what}: {dtype} [N,H,W]"
+    cap = None
+    for t, dtype, width, what in ((faces, torch.int32, 3, "faces"), (face_records, torch.uint8, 13, "face_records")):
+        if t is not None:
+            assert t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == width and t.is_contiguous(), f"{what}: {dtype} [cap,{width}]"
+            assert cap is None or cap == t.shape[0], "faces and face_records: one capacity"
+            cap = t.shape[0]
+    nbytes = cloud_mesh_workspace(N, H, W)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, points.device, "mesh")
+    _ck(lib().g2v_cloud_mesh(_p(points), _p(mask), N, H, W, MESH_MAX_EDGE if max_edge is not None else 0, float(max_edge or 0.0), _p(used),
+                             _p(vertex_of), _p(faces) if cap else None, _p(face_records) if cap else None, int(cap or 0), _p(counts),
+                             _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_mesh")
+
+
+def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=True, workspace=None):
+    """The image mesh of recon's pointmaps (g2v_cloud_mesh; include/g2vlm_hip.h has the exact rule): points fp32 [N,H,W,3], colors
+    fp32 [N,3,H,W], mask uint8 or bool [N,H,W] or None (all pixels), max_edge = the longest edge a triangle may have (None: no
+    limit).  Returns dict(vertex_records uint8 [V,15] - g2v_cloud_compact's records of the used pixels -, faces int32 [F,3],
+    face_records uint8 [F,13] (None for one switched off), used uint8 [N,H,W], vertex_of int32 [N,H,W], counts int32 [N,2]).
+    Two calls: the first only counts, the face outputs are then allocated at their exact size and the second call fills them (the
+    worst case is 25 bytes for each of 2 N (H-1) (W-1) candidates).  Synchronous: counts are read back once, and
+    size the vertex records as well."""
+    N, H, W = _nhw3(points, "points")
+    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
+        "colors: fp32 [N,3,H,W], contiguous"
+    dev = points.device
+    counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
+    cloud_mesh_raw(points, mask, max_edge, counts, workspace=workspace)
+    nv, nf = counts.sum(0, dtype=torch.int64).tolist()
+    used = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    vertex_of = torch.empty((N, H, W), dtype=torch.int32, device=dev)
+    f = torch.empty((nf, 3), dtype=torch.int32, device=dev) if faces else None
+    fr = torch.empty((nf, 13), dtype=torch.uint8, device=dev) if face_records else None
+    cloud_mesh_raw(points, mask, max_edge, counts, used, vertex_of, f, fr, workspace=workspace)
+    vertex_records = torch.empty((nv, 15), dtype=torch.uint8, device=dev)
+    per_view = torch.empty(N, dtype=torch.int32, device=dev)
+    ws = _cloud_workspace(cloud_compact_workspace(N, H, W), dev, "compact")
+    _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(used), N, H, W, _p(vertex_records) if nv else None, nv, _p(per_view), _p(ws),
+                                ws.numel() * ws.element_size(), _stream()), "g2v_cloud_compact")
+    return dict(vertex_records=vertex_records, faces=f, face_records=fr, used=used, vertex_of=vertex_of, counts=counts)
+
+
 # ------------------------------------------------------------------------------------------ voxel downsampling (csrc/voxel.hip)
-VOXEL_NO_RUNS = 1                                           # G2V_VOXEL_NO_RUNS (A/B only)
+VOXEL_NO_RUNS = 1                                          # G2V_VOXEL_NO_RUNS (A/B only)
 
 
 def _voxel_inputs(points, mask):

@@ -360,6 +360,26 @@ def write_ply_records(path, records_u8):
         f.write(np.ascontiguousarray(rec).tobytes())
 
 
+def write_ply_mesh(path, vertex_records_u8, face_records_u8):
+    """A triangle mesh as binary little-endian PLY from records that are packed already: vertices uint8 [V, 15] as for
+    write_ply_records (and under its header text), faces uint8 [F, 13], each u1 3 + <i4 a, b, c as hip.cloud_mesh leaves them -
+    the `property list uchar int vertex_indices` that mesh viewers read."""
+    def host_u8(r, width, what):
+        r = r.numpy() if torch.is_tensor(r) else np.asarray(r)
+        if r.dtype != np.uint8 or r.ndim != 2 or r.shape[1] != width:
+            raise ValueError(f"write_ply_mesh: {what} uint8 [M, {width}] expected, got {r.dtype} {r.shape}")
+        return np.ascontiguousarray(r)
+    vert, face = host_u8(vertex_records_u8, 15, "vertices"), host_u8(face_records_u8, 13, "faces")
+    hdr = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {vert.shape[0]}\n"
+           "property float x\nproperty float y\nproperty float z\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+           f"element face {face.shape[0]}\nproperty list uchar int vertex_indices\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(vert.tobytes())
+        f.write(face.tobytes())
+
+
 def conf_logit_threshold(p):
     """The confidence threshold of the point-cloud filters as the logit the device compares with: log(p / (1 - p)) in fp64,
     rounded to fp32 once, so that `conf > threshold` on the logits is an exact statement.  p is a probability in (0, 1)."""

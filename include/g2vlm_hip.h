@@ -536,6 +536,41 @@ int64_t g2v_voxel_reduce_workspace(int64_t M);
 int g2v_voxel_reduce(const void* points, const void* colors, const void* voxel_of, int N, int H, int W, double voxel_size,
                      double origin_x, double origin_y, double origin_z, int64_t M, void* records, void* counts, void* out_points,
                      void* out_colors, void* workspace, int64_t workspace_bytes, int flags, void* stream);
+
+/* ---- triangle-mesh export (csrc/mesh.hip): the pixel grid of every view triangulated -----------------------------------------
+ * points fp32 [N,H,W,3], mask u8 [N,H,W] or NULL (all pixels), max_edge fp32, read only with G2V_MESH_MAX_EDGE in flags.
+ *
+ * The rule is exact: fp32 throughout, every operation rounded once, no fused multiply-add, every comparison an IEEE compare
+ * (false on NaN).  The squared length of the edge between points A and B is d = A - B; e2 = (d0 d0 + d1 d1) + d2 d2.
+ * In view i the quad (y, x), 0 <= y < H-1, 0 <= x < W-1, has the corners p00 = (y, x), p01 = (y, x+1), p10 = (y+1, x),
+ * p11 = (y+1, x+1); with H < 2 or W < 2 there are no quads and the result is valid and empty.  Its candidate triangles, by how
+ * many corners the mask keeps:
+ *   4, and e2(p01, p10) < e2(p00, p11) (the anti diagonal is shorter):   (p00, p10, p01) then (p01, p10, p11);
+ *   4 otherwise (ties and NaN included: the main diagonal):              (p00, p10, p11) then (p00, p11, p01);
+ *   3: the one triangle of the kept corners - (p00, p10, p01), (p01, p10, p11), (p00, p10, p11) or (p00, p11, p01) when p11, p00,
+ *      p01 or p10 is the missing one;  fewer: none.
+ * All four orders face the camera: for an OpenCV camera (x right, y down, z forward) (B - A) x (C - A) points towards the camera
+ * centre.  With G2V_MESH_MAX_EDGE a candidate survives iff e2 <= max_edge max_edge holds for each of its three edges, the product
+ * formed once in fp32 (an edge with a NaN fails); without it every candidate survives, non-finite vertices included, as
+ * non-finite points survive g2v_cloud_compact.
+ * Faces are the surviving candidates in view-major, quad row-major order, within a quad in the order above.  Vertices are the
+ * pixels that the mask keeps and that at least one face references (`used`), in flat pixel order (i H + y) W + x; a vertex's id is
+ * its rank among the used pixels of all views, and faces hold vertex ids.  A vertex record is g2v_cloud_compact's 15-byte record:
+ * call it with `used` as the mask.  A face record is 13 bytes: u1 3; <i4 a, b, c.
+ *
+ * Outputs, each optional (NULL) except counts: used u8 [N,H,W]; vertex_of int32 [N,H,W] = the id or -1; faces int32
+ * [max_faces,3]; face_records u8 [max_faces,13]; counts int32 [N,2] = the vertices and faces of every view, always their true
+ * numbers.  Faces past max_faces are not written (2 N (H-1) (W-1) always suffices; 0 only counts).  Positions are integer
+ * prefix sums: the bytes are the same on every run.  The workspace needs no initialisation.
+ * -22 before any launch for a dimension <= 0, N > 65535, N H W or 2 N (H-1) (W-1) above 2^31 - 1 (ids and face counts are int32),
+ * points, counts or workspace NULL, an unknown flag, a max_edge that is negative or NaN with the flag set, max_faces < 0, an fp32 /
+ * int32 pointer that is not 4-byte aligned and a workspace smaller than the query says; the query returns 0 for every shape that
+ * the entry point refuses.  Up to five launches on the stream; hipGraph-capturable, no host synchronisation.  */
+#define G2V_MESH_MAX_EDGE 1
+int64_t g2v_cloud_mesh_workspace(int N, int H, int W);
+int g2v_cloud_mesh(const void* points, const void* mask, int N, int H, int W, int flags, float max_edge, void* used,
+                   void* vertex_of, void* faces, void* face_records, int64_t max_faces, void* counts, void* workspace,
+                   int64_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,9 @@ Flags of this project's own, all off by default (without them main() does what t
 matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cloud on the device before it is written;
 --min-views, --max-in-front (with --consistency-rtol) add the multi-view consistency filter (point_cloud_mask);
 --render-dir writes one PNG per input view, re-rendered from the OTHER views' points (render_point_cloud, under the filters given),
---render-orbit F adds F turntable frames there, --render-radius and --render-size set the splat half-width and the image size."""
+--render-orbit F adds F turntable frames there, --render-radius and --render-size set the splat half-width and the image size;
+--mesh PATH also writes the reconstruction as a triangle mesh (save_mesh, under the filters given; --mesh-max-edge L drops triangles
+with an edge longer than L)."""
 import argparse
 import os
 import sys
@@ -38,6 +40,22 @@ parser.add_argument("--render-orbit", type=int, default=None, metavar="F",
                     help="with --render-dir: also write orbit_000.png ..., F turntable frames through the scene's own cameras")
 parser.add_argument("--render-radius", type=int, default=1, metavar="R", help="with --render-dir: a point is drawn as a square of 2R+1 pixels (0..8)")
 parser.add_argument("--render-size", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --render-dir: the size of the rendered images")
+parser.add_argument("--mesh", type=str, default=None, metavar="PATH",
+                    help="also write the reconstruction as a triangle mesh (binary PLY with faces): every view's pixel grid triangulated")
+parser.add_argument("--mesh-max-edge", type=float, default=None, metavar="L", help="with --mesh: drop triangles with an edge longer than L")
+
+
+def write_mesh(pred, args):
+    """--mesh: the mesh under the filters given on the command line; with no filter flag at all, save_mesh's defaults (edge_rtol = 0.03)"""
+    from g2vlm_utils import point_cloud_mask, save_mesh
+    if args.min_views is not None or args.max_in_front is not None or args.edge_rtol is not None or args.edge_atol is not None \
+            or args.conf_threshold is not None:
+        consistency = {}
+        if args.min_views is not None or args.max_in_front is not None:
+            consistency = dict(min_views=args.min_views, max_in_front=args.max_in_front, depth_rtol=args.consistency_rtol)
+        mask = point_cloud_mask(pred, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol, **consistency)
+        return save_mesh(pred, args.mesh, mask=mask, max_edge=args.mesh_max_edge)
+    return save_mesh(pred, args.mesh, max_edge=args.mesh_max_edge)
 
 
 def render_views(pred, args):
@@ -64,6 +82,8 @@ def main(argv=None):
         parser.error("--render-orbit F needs --render-dir and F >= 1")
     if not 0 <= args.render_radius <= 8:
         parser.error("--render-radius must be in 0..8")
+    if args.mesh_max_edge is not None and (args.mesh is None or not args.mesh_max_edge >= 0):
+        parser.error("--mesh-max-edge L needs --mesh and L >= 0")
     names = sorted(n for n in os.listdir(args.image_folder) if n.lower().endswith((".png", ".jpg", ".jpeg")))
     image_names = [os.path.join(args.image_folder, n) for n in names]
     print(image_names)
@@ -83,6 +103,8 @@ def main(argv=None):
         save_ply_visualization(pred, args.save_path)
     if args.render_dir is not None:
         render_views(pred, args)
+    if args.mesh is not None:
+        write_mesh(pred, args)
     if args.intrinsics:
         from g2vlm_utils import estimate_intrinsics
         # over every valid pixel: X/Z and Y/Z of a local point (xy z, z) do not depend on its depth, so the depth filters have
