@@ -260,18 +260,10 @@ class OracleG2VLM:
         q = q.to(self.cd).transpose(0, 1)
         k = k.to(self.cd).transpose(0, 1)
         v = v.to(self.cd)
-        if cache is not None and cache.key_cache[i] is not None:
-            pk, pv = cache.key_cache[i], cache.value_cache[i]
-            tot = int(sum(query_lens)) + int(sum(key_values_lens))
-            mk = pk.new_zeros((tot, nkv, hd)); mv = pk.new_zeros((tot, nkv, hd))
-            mk[packed_query_indexes] = k; mk[packed_key_value_indexes] = pk
-            mv[packed_query_indexes] = v; mv[packed_key_value_indexes] = pv
-            kv_lens = key_values_lens + query_lens
-        else:
-            mk, mv, kv_lens = k, v, query_lens
+        mk, mv, kv_lens = self.merge_kv(i, k, v, cache, query_lens, packed_query_indexes, key_values_lens, packed_key_value_indexes)
         cu_q = F.pad(torch.cumsum(query_lens, 0), (1, 0))
         cu_k = F.pad(torch.cumsum(kv_lens, 0), (1, 0))
-        o = varlen_attention(q, mk, mv, cu_q, cu_k, is_causal, precise=self.precise)
+        o = self.varlen(q, mk, mv, cu_q, cu_k, is_causal)
         o = o.reshape(-1, nh * hd)
         if mode == "und":
             o = self.lin(o, a + "o_proj", bias=False)
@@ -281,6 +273,23 @@ class OracleG2VLM:
         if cache is not None:
             cache.key_cache[i], cache.value_cache[i] = mk, mv
         return o
+
+    def merge_kv(self, i, k, v, cache, query_lens, packed_query_indexes, key_values_lens, packed_key_value_indexes):
+        """The cache merge of PackedAttentionMoT.forward_inference (qwen2vl.py:619-640): the new rows at packed_query_indexes,
+        the past rows at packed_key_value_indexes.  Returns (keys, values, key lengths per sample)."""
+        if cache is None or cache.key_cache[i] is None:
+            return k, v, query_lens
+        nkv, hd = k.shape[1], k.shape[2]
+        pk, pv = cache.key_cache[i], cache.value_cache[i]
+        tot = int(sum(query_lens)) + int(sum(key_values_lens))
+        mk = pk.new_zeros((tot, nkv, hd)); mv = pk.new_zeros((tot, nkv, hd))
+        mk[packed_query_indexes] = k; mk[packed_key_value_indexes] = pk
+        mv[packed_query_indexes] = v; mv[packed_key_value_indexes] = pv
+        return mk, mv, key_values_lens + query_lens
+
+    def varlen(self, q, k, v, cu_q, cu_k, causal):
+        """Every flash_attn_varlen_func call site goes through here (tests/block_check.py overrides it)."""
+        return varlen_attention(q, k, v, cu_q, cu_k, causal, precise=self.precise)
 
     def _mlp(self, x, name):
         """Qwen2MLP.forward (modeling_qwen2_vl.py:519-521); every op result rounds to bf16."""
@@ -376,7 +385,7 @@ class OracleG2VLM:
         q = self.lin(h, p + "attention.attention.query").view(x.shape[0], nh, -1)
         k = self.lin(h, p + "attention.attention.key").view(x.shape[0], nh, -1)
         v = self.lin(h, p + "attention.attention.value").view(x.shape[0], nh, -1)
-        ctx = varlen_attention(q, k, v, cu, cu, False, precise=self.precise).reshape(x.shape[0], -1)
+        ctx = self.varlen(q, k, v, cu, cu, False).reshape(x.shape[0], -1)
         a = self.lin(ctx, p + "attention.output.dense")
         x = a * self.sd[p + "layer_scale1.lambda1"] + x
         m = self.lin(F.gelu(self.lin(self.ln(x, p + "norm2"), p + "mlp.fc1")), p + "mlp.fc2")
@@ -433,7 +442,7 @@ class OracleG2VLM:
             qf, kf = q.float(), k.float()
             q = ((qf * c) + (rotate_half(qf) * s)).to(self.cd)
             k = ((kf * c) + (rotate_half(kf) * s)).to(self.cd)
-            o = varlen_attention(q, k, v, cu, cu, False, precise=self.precise).reshape(n, -1)
+            o = self.varlen(q, k, v, cu, cu, False).reshape(n, -1)
             x = x + self.lin(o, p + "attn.proj")
             hdn = self.lin(self.ln(x, p + "norm2"), p + "mlp.fc1")
             hdn = hdn * torch.sigmoid(1.702 * hdn)                               # quick_gelu, bf16 ops
