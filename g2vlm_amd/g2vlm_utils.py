@@ -508,6 +508,238 @@ def save_mesh(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_at
     return dict(num_vertices=nv, num_faces=nf, counts=counts)
 
 
+# ---- evaluation against ground truth (csrc/nn.hip) ---------------------------------------------------------------------------
+def _points3(t, what):
+    if not torch.is_tensor(t) or not t.is_floating_point() or t.dim() < 1 or t.shape[-1] != 3:
+        raise ValueError(f"{what}: a floating-point tensor [...,3] expected, got "
+                         f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+    return t
+
+
+def _flat_mask(mask, shape, what):
+    """an optional mask over points of `shape` (without the 3) as a flat uint8 tensor, or ValueError"""
+    if mask is None:
+        return None
+    if not torch.is_tensor(mask) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tuple(shape):
+        raise ValueError(f"{what}: a bool / uint8 tensor {tuple(shape)} expected, got "
+                         f"{(mask.dtype, tuple(mask.shape)) if torch.is_tensor(mask) else type(mask).__name__}")
+    mask = mask.reshape(-1).contiguous()
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
+def _max_distance(max_distance):
+    if max_distance is None:
+        return None
+    try:
+        ok = not isinstance(max_distance, bool) and float(max_distance) >= 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"max_distance must be a number >= 0 (or None: no limit), got {max_distance!r}")
+    return float(max_distance)
+
+
+def nearest_points(query, target, max_distance=None, query_mask=None, target_mask=None):
+    """For every query point the nearest target point, on the device (hip.cloud_nn; include/g2vlm_hip.h and DESIGN.md 6p have the
+    exact rule): query and target are tensors [...,3] on the device, flattened to [Nq,3] and [Nt,3]; the masks (bool / uint8, the
+    shape of the points without the 3) drop points on either side, non-finite points never take part; max_distance is the largest
+    distance that counts.  Exact: the smallest fp32 squared distance, ties to the lowest index - no approximate search.
+    Returns dict(index int32 [Nq] = the flat target index or -1, sq_distance fp32 [Nq] (+inf without a neighbour), distance fp32
+    [Nq] = sqrt(sq_distance)).  ValueError for every bad argument, before any launch."""
+    from . import hip
+    query, target = _points3(query, "query"), _points3(target, "target")
+    max_distance = _max_distance(max_distance)
+    query_mask = _flat_mask(query_mask, query.shape[:-1], "query_mask")
+    target_mask = _flat_mask(target_mask, target.shape[:-1], "target_mask")
+    if not (query.is_cuda and target.is_cuda and query.device == target.device):
+        raise ValueError(f"query and target must be on one GPU, got {query.device} and {target.device}")
+    if query.numel() // 3 > 2 ** 31 - 1 or target.numel() // 3 > 2 ** 31 - 1:
+        raise ValueError("at most 2^31 - 1 points per side")
+    q, t = query.detach().float().reshape(-1, 3).contiguous(), target.detach().float().reshape(-1, 3).contiguous()
+    qm = None if query_mask is None else query_mask.to(q.device)
+    tm = None if target_mask is None else target_mask.to(q.device)
+    index, sq, _ = hip.cloud_nn(q, t, max_distance, qm, tm)
+    return dict(index=index, sq_distance=sq, distance=torch.sqrt(sq))
+
+
+def align_points(src, dst, mask=None, with_scale=True):
+    """Umeyama's closed-form similarity dst ~ s R src + t over corresponding points (the alignment family of the reference's
+    modeling/pi3/utils/alignment.py, here in closed form): src, dst tensors [...,3] of one shape, mask bool / uint8 [...] or None.
+    The rows that take part are those the mask keeps whose six coordinates are finite.  Means, covariance and variance are fp64
+    reductions on the tensors' device; the 3 x 3 SVD runs in fp64 on the host; det(U) det(V) < 0 (the best orthogonal fit is a
+    reflection) flips the last singular vector, so R is always a rotation.  with_scale=False fixes s = 1.
+    Returns dict(scale float, rotation fp64 [3,3], translation fp64 [3], transform fp64 [4,4] = [[s R, t], [0, 1]], num_points),
+    tensors on the host.  ValueError for bad arguments, and where fewer than 3 rows take part or src has no spread."""
+    src, dst = _points3(src, "src"), _points3(dst, "dst")
+    if src.shape != dst.shape:
+        raise ValueError(f"src and dst must have one shape, got {tuple(src.shape)} and {tuple(dst.shape)}")
+    if not isinstance(with_scale, (bool, np.bool_)):
+        raise ValueError(f"with_scale must be a bool, got {with_scale!r}")
+    mask = _flat_mask(mask, src.shape[:-1], "mask")
+    s64, d64 = src.detach().reshape(-1, 3).double(), dst.detach().reshape(-1, 3).to(src.device).double()
+    valid = torch.isfinite(s64).all(1) & torch.isfinite(d64).all(1)
+    if mask is not None:
+        valid &= mask.to(src.device) != 0
+    col = valid.unsqueeze(1)
+    zero = torch.zeros((), dtype=torch.float64, device=s64.device)
+    n = valid.sum().double()
+    mu_s, mu_d = torch.where(col, s64, zero).sum(0) / n, torch.where(col, d64, zero).sum(0) / n
+    xs, xd = torch.where(col, s64 - mu_s, zero), torch.where(col, d64 - mu_d, zero)
+    cov = (xd.t() @ xs) / n
+    var = (xs * xs).sum() / n
+    host_ = torch.cat([cov.reshape(-1), var.reshape(1), mu_s, mu_d, n.reshape(1)]).cpu().numpy()      # one copy of 17 numbers
+    cov, var, mu_s, mu_d, count = host_[:9].reshape(3, 3), host_[9], host_[10:13], host_[13:16], int(host_[16])
+    if count < 3 or not var > 0.0:
+        raise ValueError(f"align_points needs at least 3 finite corresponding points with some spread, got {count} (variance {var})")
+    U, D, Vt = np.linalg.svd(cov)
+    S = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0:
+        S[2] = -1.0
+    R = U @ np.diag(S) @ Vt
+    s = float((D * S).sum() / var) if with_scale else 1.0
+    t = mu_d - s * (R @ mu_s)
+    M = np.eye(4)
+    M[:3, :3], M[:3, 3] = s * R, t
+    return dict(scale=s, rotation=torch.from_numpy(R), translation=torch.from_numpy(t), transform=torch.from_numpy(M), num_points=count)
+
+
+def _apply_transform(M, points):
+    """rows of a 4 x 4 (numpy fp64) applied to points fp32 [n,3], op by op in fp64 - ((a0 x + a1 y) + a2 z) + t - and rounded to
+    fp32 once: the same numbers wherever it runs"""
+    p = points.double()
+    x, y, z = p[:, 0], p[:, 1], p[:, 2]
+    return torch.stack([((float(M[k, 0]) * x + float(M[k, 1]) * y) + float(M[k, 2]) * z) + float(M[k, 3]) for k in range(3)], 1).float().contiguous()
+
+
+def _eval_thresholds(thresholds):
+    try:
+        out = tuple(float(t) for t in thresholds)
+        ok = all(not isinstance(t, bool) for t in thresholds) and all(t > 0.0 and np.isfinite(t) for t in out)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"thresholds must be a sequence of finite numbers > 0, got {thresholds!r}")
+    return out
+
+
+def _metrics_from_distances(acc_sq, acc_found, comp_sq, comp_found, thresholds, max_distance):
+    """The metrics of evaluate_reconstruction from the two nearest-neighbour results: *_sq fp32 squared distances of the points that
+    take part on each side (+inf without a neighbour), *_found bool.  fp64 throughout."""
+    out = dict(n_pred=int(acc_sq.numel()), n_gt=int(comp_sq.numel()), thresholds=tuple(thresholds))
+    nan = float("nan")
+    dist = {}
+    for name, sq in (("accuracy", acc_sq), ("completeness", comp_sq)):
+        d = torch.sqrt(sq.double())
+        if max_distance is not None:
+            d = torch.clamp(d, max=float(max_distance))
+        dist[name] = d
+        if d.numel():
+            s = torch.sort(d).values
+            out[name], out[name + "_median"] = float(d.mean()), float(0.5 * (s[(d.numel() - 1) // 2] + s[d.numel() // 2]))
+        else:
+            out[name] = out[name + "_median"] = nan
+    out["chamfer"] = 0.5 * (out["accuracy"] + out["completeness"])
+    out["precision"], out["recall"], out["fscore"], out["precision_hits"], out["recall_hits"] = [], [], [], [], []
+    for T in thresholds:
+        ha = int((acc_found & (acc_sq.double() <= T * T)).sum())
+        hc = int((comp_found & (comp_sq.double() <= T * T)).sum())
+        p = ha / out["n_pred"] if out["n_pred"] else nan
+        r = hc / out["n_gt"] if out["n_gt"] else nan
+        f = nan if (p != p or r != r) else (2 * p * r / (p + r) if p + r > 0 else 0.0)
+        for key, v in (("precision", p), ("recall", r), ("fscore", f), ("precision_hits", ha), ("recall_hits", hc)):
+            out[key].append(v)
+    return out, dist
+
+
+def evaluate_reconstruction(pred_dict, gt_points, gt_mask=None, align="sim3", thresholds=(0.05,), max_distance=None, mask=None,
+                            conf_threshold=None, edge_rtol=None, edge_atol=None, filter_nan=True, return_distances=False):
+    """A recon result measured against a ground-truth cloud, on the device (two exact nearest-neighbour searches, hip.cloud_nn;
+    DESIGN.md 6p).  The predicted cloud is the pixels point_cloud_mask keeps under the same filter arguments; an explicit mask (bool
+    / uint8 [N,H,W]) replaces the filters and may not be combined with them.  Non-finite points take no part on either side.
+    gt_points: [N,H,W,3] (or [1,N,H,W,3]), pixel-aligned with the prediction - then align="sim3" fits Umeyama's similarity
+    (align_points) on the pixels valid on both sides and applies it to the prediction -, or an unordered cloud [M,3], for which
+    align must be "none" or a 4 x 4 similarity to apply (no correspondences: nothing to fit; ICP is not provided).  gt_mask: bool /
+    uint8 of the ground truth's shape without the 3.
+    Returns dict(accuracy = the mean distance from a predicted point to its nearest ground-truth point, completeness = the other
+    direction, chamfer = their mean, accuracy_median, completeness_median, thresholds, precision / recall / fscore = a list with
+    one entry per threshold (the share of predicted / ground-truth points with a neighbour within it; 2 p r / (p + r)),
+    precision_hits / recall_hits = the counts, n_pred, n_gt, transform fp64 [4,4]); with return_distances=True also
+    accuracy_distances / completeness_distances fp64 and pred_points fp32 [n_pred,3] = the aligned prediction, on the device.
+    Distances are fp64 square roots of the kernel's fp32 squared distances and means are fp64.  With max_distance a neighbour
+    farther away does not count: such a point is a miss at every threshold and enters the means and medians with max_distance
+    itself (clipping).  An empty side gives NaN for its mean, median and rate (and for chamfer and fscore); without max_distance a
+    point of the other side then has distance +inf.  ValueError for every bad argument, before any launch."""
+    from . import hip
+    thresholds = _eval_thresholds(thresholds)
+    max_distance = _max_distance(max_distance)
+    if not isinstance(return_distances, (bool, np.bool_)):
+        raise ValueError(f"return_distances must be a bool, got {return_distances!r}")
+    if mask is not None:
+        given = [k for k, v, d in (("conf_threshold", conf_threshold, None), ("edge_rtol", edge_rtol, None), ("edge_atol", edge_atol, None),
+                                   ("filter_nan", filter_nan, True)) if not (v is d or v == d)]
+        if given:
+            raise ValueError(f"an explicit mask replaces the filters: {', '.join(given)} may not be given with it")
+    points, local, conf, _, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=False)
+    n, h, w = points.shape[:3]
+    gt = _points3(gt_points, "gt_points")
+    if gt.dim() == 5 and gt.shape[0] == 1:
+        gt = gt[0]
+        if torch.is_tensor(gt_mask) and gt_mask.dim() == 4 and gt_mask.shape[0] == 1:
+            gt_mask = gt_mask[0]
+    if gt.dim() == 4:
+        if tuple(gt.shape[:3]) != (n, h, w):
+            raise ValueError(f"gt_points {tuple(gt.shape)} is not pixel-aligned with the prediction [{n},{h},{w},3]")
+    elif gt.dim() != 2:
+        raise ValueError(f"gt_points: [N,H,W,3] pixel-aligned with the prediction or an unordered cloud [M,3] expected, got {tuple(gt.shape)}")
+    gm = _flat_mask(gt_mask, gt.shape[:-1], "gt_mask")
+    M = None
+    if isinstance(align, str):
+        if align not in ("sim3", "none"):
+            raise ValueError(f"align must be 'sim3', 'none' or a 4 x 4 similarity, got {align!r}")
+        if align == "sim3" and gt.dim() != 4:
+            raise ValueError("align='sim3' needs pixel-aligned gt_points [N,H,W,3]: an unordered cloud has no correspondences to fit "
+                             "(pass align='none' or a 4 x 4 similarity)")
+    else:
+        try:
+            M = np.array(align.detach().cpu().numpy() if torch.is_tensor(align) else align, dtype=np.float64)
+        except (TypeError, ValueError):
+            M = None
+        if M is None or M.shape != (4, 4) or not np.isfinite(M).all() or M[3].tolist() != [0.0, 0.0, 0.0, 1.0]:
+            raise ValueError("align: 'sim3', 'none' or a finite 4 x 4 matrix with the last row (0, 0, 0, 1) expected")
+    if mask is not None:
+        keep = _voxel_mask(mask, points.shape[:3], points.device)
+    else:
+        keep = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    dev = points.device
+    P, pm = points.reshape(-1, 3), keep.reshape(-1)
+    G = gt.detach().to(dev).float().reshape(-1, 3).contiguous()
+    gm = None if gm is None else gm.to(dev)
+    if isinstance(align, str) and align == "sim3":
+        both = pm != 0 if gm is None else (pm != 0) & (gm != 0)
+        M = align_points(P, G, mask=both)["transform"].numpy()
+    Pa = P if M is None else _apply_transform(M, P)
+    idx_a, sq_a, _ = hip.cloud_nn(Pa, G, max_distance, pm, gm)
+    idx_c, sq_c, _ = hip.cloud_nn(G, Pa, max_distance, gm, pm)
+    part_a = (pm != 0) & torch.isfinite(Pa).all(1)
+    part_c = torch.isfinite(G).all(1) if gm is None else (gm != 0) & torch.isfinite(G).all(1)
+    out, dist = _metrics_from_distances(sq_a[part_a], idx_a[part_a] >= 0, sq_c[part_c], idx_c[part_c] >= 0, thresholds, max_distance)
+    out["transform"] = torch.from_numpy(np.eye(4) if M is None else M.copy())
+    if return_distances:
+        out.update(accuracy_distances=dist["accuracy"], completeness_distances=dist["completeness"], pred_points=Pa[part_a])
+    return out
+
+
+def format_evaluation(result):
+    """evaluate_reconstruction's result as the lines of a small table"""
+    lines = [f"{'points':<22}{result['n_pred']:>12} predicted {result['n_gt']:>12} ground truth",
+             f"{'accuracy (mean)':<22}{result['accuracy']:>12.6f}   median {result['accuracy_median']:.6f}",
+             f"{'completeness (mean)':<22}{result['completeness']:>12.6f}   median {result['completeness_median']:.6f}",
+             f"{'chamfer':<22}{result['chamfer']:>12.6f}"]
+    for T, p, r, f in zip(result["thresholds"], result["precision"], result["recall"], result["fscore"]):
+        lines.append(f"{'at ' + format(T, 'g'):<22}precision {p:.4f}   recall {r:.4f}   fscore {f:.4f}")
+    return lines
+
+
 # ---- rendering the cloud from any camera (csrc/render.hip) -------------------------------------------------------------------
 def _is_int(x):
     return not isinstance(x, bool) and isinstance(x, (int, np.integer))

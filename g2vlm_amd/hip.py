@@ -114,6 +114,8 @@ _SIGS = {
     "g2v_cloud_render": ([_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_cloud_mesh_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_cloud_mesh": ([_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_nn_workspace": ([_L, _L], C.c_int64),
+    "g2v_cloud_nn": ([_P, _P, _L, _P, _P, _L, _F, _I, _P, _P, _P, _P, _L, _P], C.c_int),
     "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
@@ -1182,6 +1184,53 @@ def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=Tru
     _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(used), N, H, W, _p(vertex_records) if nv else None, nv, _p(per_view), _p(ws),
                                 ws.numel() * ws.element_size(), _stream()), "g2v_cloud_compact")
     return dict(vertex_records=vertex_records, faces=f, face_records=fr, used=used, vertex_of=vertex_of, counts=counts)
+
+
+# ------------------------------------------------------------------------------------------ nearest neighbour (csrc/nn.hip)
+NN_BRUTE, NN_GRID = 1, 2                                    # G2V_NN_BRUTE, G2V_NN_GRID (A/B and tests only)
+
+
+def cloud_nn_workspace(Nq, Nt):
+    return int(lib().g2v_cloud_nn_workspace(int(Nq), int(Nt)))
+
+
+def cloud_nn_raw(query, query_mask, target, target_mask, max_distance, flags, index, sq_distance, stats, workspace=None):
+    """One call of g2v_cloud_nn into the caller's tensors (no allocation but a grown workspace, no host synchronisation)."""
+    for t, what in ((query, "query"), (target, "target")):
+        assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous(), f"{what}: fp32 [N,3], contiguous"
+    Nq, Nt = query.shape[0], target.shape[0]
+    masks = []
+    for m, n, what in ((query_mask, Nq, "query_mask"), (target_mask, Nt, "target_mask")):
+        if m is not None:
+            if m.dtype == torch.bool:
+                m = m.view(torch.uint8)
+            assert m.is_cuda and m.dtype == torch.uint8 and tuple(m.shape) == (n,) and m.is_contiguous(), f"{what}: uint8 [{n}]"
+        masks.append(m)
+    assert index.is_cuda and index.dtype == torch.int32 and tuple(index.shape) == (Nq,) and index.is_contiguous(), "index: int32 [Nq]"
+    assert sq_distance.is_cuda and sq_distance.dtype == torch.float32 and tuple(sq_distance.shape) == (Nq,) and sq_distance.is_contiguous(), \
+        "sq_distance: fp32 [Nq]"
+    assert stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (4,), "stats: int32 [4]"
+    nbytes = cloud_nn_workspace(Nq, Nt)
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, query.device, "nn")
+    _ck(lib().g2v_cloud_nn(_p(query) if Nq else None, _p(masks[0]) if Nq else None, Nq, _p(target) if Nt else None,
+                           _p(masks[1]) if Nt else None, Nt, float("inf") if max_distance is None else float(max_distance), int(flags),
+                           _p(index) if Nq else None, _p(sq_distance) if Nq else None, _p(stats), _p(workspace),
+                           workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_nn")
+
+
+def cloud_nn(query, target, max_distance=None, query_mask=None, target_mask=None, flags=0, workspace=None):
+    """For every query point the nearest target point (g2v_cloud_nn; include/g2vlm_hip.h has the exact rule): query fp32 [Nq,3],
+    target fp32 [Nt,3], masks uint8 or bool [Nq] / [Nt] or None (all points), max_distance = the largest distance that counts (None:
+    no limit).  Returns (index int32 [Nq] = the target or -1, sq_distance fp32 [Nq] = the fp32 squared distance or +inf, stats int32
+    [4] = participating queries, participating targets, queries without / with a neighbour), on the device.  Exact: the nearest by
+    the fp32 rule, ties to the lowest index; bit-reproducible; no host synchronisation.  flags: NN_BRUTE / NN_GRID force a path."""
+    dev = query.device
+    index = torch.empty(query.shape[0], dtype=torch.int32, device=dev)
+    sq_distance = torch.empty(query.shape[0], dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.int32, device=dev)
+    cloud_nn_raw(query, query_mask, target, target_mask, max_distance, flags, index, sq_distance, stats, workspace=workspace)
+    return index, sq_distance, stats
 
 
 # ------------------------------------------------------------------------------------------ voxel downsampling (csrc/voxel.hip)

@@ -571,6 +571,36 @@ int64_t g2v_cloud_mesh_workspace(int N, int H, int W);
 int g2v_cloud_mesh(const void* points, const void* mask, int N, int H, int W, int flags, float max_edge, void* used,
                    void* vertex_of, void* faces, void* face_records, int64_t max_faces, void* counts, void* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* ---- exact nearest neighbour between two clouds (csrc/nn.hip) ------------------------------------------------------------------
+ * query fp32 [Nq,3], target fp32 [Nt,3], query_mask u8 [Nq] / target_mask u8 [Nt] or NULL (all points), max_distance fp32.
+ *
+ * The rule is exact: a point takes part if its mask byte is non-zero and its three coordinates are finite.  For a participating
+ * pair, in fp32 with every operation rounded once and no fused multiply-add: d = q - t, d2 = (d0 d0 + d1 d1) + d2 d2 (never NaN;
+ * +inf by overflow is possible).  m2 = max_distance max_distance, one fp32 product; a target counts unless d2 > m2 (equality
+ * counts; max_distance = +inf, or any value whose square overflows, is no limit).  The answer of a query is the minimum over the
+ * counting targets of the 64-bit key bits(d2) << 32 | target index: the nearest target, ties to the lowest index, and the lowest
+ * participating index where every d2 is +inf.  index int32 [Nq] and sq_distance fp32 [Nq] hold the key's two halves; a query that
+ * takes no part or has no counting target gets -1 and +inf.  stats int32 [4] = {participating queries, participating targets,
+ * participating queries without a neighbour, participating queries with one}.  Nq == 0 and Nt == 0 are valid calls.
+ * The minimum of integer keys does not depend on the order in which the targets are visited: the bytes of the three outputs are
+ * the same on every run and on both paths.  G2V_NN_BRUTE / G2V_NN_GRID (A/B and tests only) force a path: every query against
+ * every target through LDS tiles, or a uniform grid of cubic cells over the targets' bounding box (at most G^3 cells, G = the
+ * largest G with G^3 <= 2 Nt, at most 256) walked ring by ring until no unvisited cell can hold a smaller key (DESIGN.md 6p has the argument).
+ * Without a flag the brute path runs for every Nt: it was the faster one at every size measured.
+ *
+ * The workspace (16-byte aligned, no initialisation needed) is 256 + 24 Nt + 8 Nq + 4 (G^3 + 1) + 4 ceil(G^3 / 1024) bytes.
+ * -22 before any launch for Nq or Nt < 0 or above 2^31 - 1, a max_distance that is negative or NaN, an unknown flag or both path
+ * flags, stats or workspace NULL, query, index or sq_distance NULL with Nq > 0, target NULL with Nt > 0, an fp32 / int32 pointer
+ * that is not 4-byte aligned, a workspace that is not 16-byte aligned or smaller than the query says; the query returns 0 for
+ * counts that the entry point refuses.  Eleven launches on the grid path; on the brute path five plus one per 2^36 pairs (the
+ * targets are cut so that no single kernel holds a device for long).  One stream; hipGraph-capturable, no host synchronisation.  */
+#define G2V_NN_BRUTE 1
+#define G2V_NN_GRID 2
+int64_t g2v_cloud_nn_workspace(int64_t Nq, int64_t Nt);
+int g2v_cloud_nn(const void* query, const void* query_mask, int64_t Nq, const void* target, const void* target_mask, int64_t Nt,
+                 float max_distance, int flags, void* index, void* sq_distance, void* stats, void* workspace,
+                 int64_t workspace_bytes, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,10 @@ matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cl
 --render-dir writes one PNG per input view, re-rendered from the OTHER views' points (render_point_cloud, under the filters given),
 --render-orbit F adds F turntable frames there, --render-radius and --render-size set the splat half-width and the image size;
 --mesh PATH also writes the reconstruction as a triangle mesh (save_mesh, under the filters given; --mesh-max-edge L drops triangles
-with an edge longer than L)."""
+with an edge longer than L); --evaluate GT.npy measures the reconstruction against a ground-truth cloud (evaluate_reconstruction, under
+the filters given: a [N,H,W,3] array pixel-aligned with the views, or an unordered [M,3] cloud with --eval-align none) and prints
+accuracy, completeness, Chamfer distance and precision / recall / F-score at every --eval-threshold T; --eval-max-distance D clips
+the search, --eval-align sim3|none picks the alignment."""
 import argparse
 import os
 import sys
@@ -43,6 +46,55 @@ parser.add_argument("--render-size", type=int, nargs=2, default=None, metavar=("
 parser.add_argument("--mesh", type=str, default=None, metavar="PATH",
                     help="also write the reconstruction as a triangle mesh (binary PLY with faces): every view's pixel grid triangulated")
 parser.add_argument("--mesh-max-edge", type=float, default=None, metavar="L", help="with --mesh: drop triangles with an edge longer than L")
+parser.add_argument("--evaluate", type=str, default=None, metavar="GT.npy",
+                    help="measure the reconstruction against ground-truth points: a .npy of shape [N,H,W,3] (pixel-aligned) or [M,3]")
+parser.add_argument("--eval-threshold", type=float, action="append", default=None, metavar="T",
+                    help="with --evaluate: a distance at which precision / recall / F-score are reported (repeatable; default 0.05)")
+parser.add_argument("--eval-max-distance", type=float, default=None, metavar="D",
+                    help="with --evaluate: neighbours farther than D do not count (such points are misses, and enter the means with D)")
+parser.add_argument("--eval-align", type=str, default=None, choices=("sim3", "none"),
+                    help="with --evaluate: fit a similarity on the pixels valid on both sides (default for [N,H,W,3]) or compare as is")
+
+
+def check_evaluation_flags(args):
+    """refuses malformed --evaluate / --eval-* values (parser.error) and returns the ground truth array or None"""
+    import numpy as np
+    if args.evaluate is None:
+        if args.eval_threshold is not None or args.eval_max_distance is not None or args.eval_align is not None:
+            parser.error("--eval-threshold, --eval-max-distance and --eval-align need --evaluate GT.npy")
+        return None
+    for t in args.eval_threshold or ():
+        if not (t > 0 and np.isfinite(t)):
+            parser.error("--eval-threshold T must be finite and > 0")
+    if args.eval_max_distance is not None and not args.eval_max_distance >= 0:
+        parser.error("--eval-max-distance D must be >= 0")
+    try:
+        gt = np.load(args.evaluate, allow_pickle=False)
+    except (OSError, ValueError) as e:
+        parser.error(f"--evaluate {args.evaluate}: {e}")
+    if gt.dtype.kind != "f" or gt.ndim not in (2, 4) or gt.shape[-1] != 3:
+        parser.error(f"--evaluate {args.evaluate}: a float array [N,H,W,3] or [M,3] expected, got {gt.dtype} {gt.shape}")
+    if gt.ndim == 2 and args.eval_align == "sim3":
+        parser.error("--eval-align sim3 needs pixel-aligned ground truth [N,H,W,3]")
+    return gt
+
+
+def evaluate(pred, args, gt):
+    """--evaluate: the table, under the filters given on the command line"""
+    import torch
+    from g2vlm_utils import evaluate_reconstruction, point_cloud_mask
+    from g2vlm_amd.g2vlm_utils import format_evaluation
+    consistency = {}
+    if args.min_views is not None or args.max_in_front is not None:
+        consistency = dict(min_views=args.min_views, max_in_front=args.max_in_front, depth_rtol=args.consistency_rtol)
+    mask = point_cloud_mask(pred, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol, **consistency)
+    align = args.eval_align or ("sim3" if gt.ndim == 4 else "none")
+    result = evaluate_reconstruction(pred, torch.from_numpy(gt).float(), align=align, thresholds=tuple(args.eval_threshold or (0.05,)),
+                                     max_distance=args.eval_max_distance, mask=mask)
+    print(f"{args.evaluate}: align {align}")
+    for line in format_evaluation(result):
+        print(line)
+    return result
 
 
 def write_mesh(pred, args):
@@ -84,6 +136,7 @@ def main(argv=None):
         parser.error("--render-radius must be in 0..8")
     if args.mesh_max_edge is not None and (args.mesh is None or not args.mesh_max_edge >= 0):
         parser.error("--mesh-max-edge L needs --mesh and L >= 0")
+    gt = check_evaluation_flags(args)
     names = sorted(n for n in os.listdir(args.image_folder) if n.lower().endswith((".png", ".jpg", ".jpeg")))
     image_names = [os.path.join(args.image_folder, n) for n in names]
     print(image_names)
@@ -105,6 +158,8 @@ def main(argv=None):
         render_views(pred, args)
     if args.mesh is not None:
         write_mesh(pred, args)
+    if gt is not None:
+        pred["evaluation"] = evaluate(pred, args, gt)
     if args.intrinsics:
         from g2vlm_utils import estimate_intrinsics
         # over every valid pixel: X/Z and Y/Z of a local point (xy z, z) do not depend on its depth, so the depth filters have
