@@ -63,13 +63,34 @@ def synth_images(n, h, w, seed):
     return torch.randn((n, 3, h, w), generator=g)
 
 
-CD = [torch.bfloat16]        # "autocast" compute dtype; forward(precise=True) runs the same graph in fp32 (error-growth yardstick)
+class Ops:
+    """The sums of the encoder, overridable as OracleG2VLM.lin / varlen are: a subclass may take them in another order or plant
+    a fault (tests/dinov3_block_check.py); the defaults are the reference's.
+
+    precise: the same graph with fp32 weights and activations and fp64 attention - the yardstick every bf16 run is measured
+    against.  round_qk: the rotated q/k are rounded to bf16 before attention, which the reference does not do (it hands fp32 to
+    the attention) and a real flash kernel must: the engine's one documented deviation, so its specification is round_qk=True."""
+
+    def __init__(self, precise=False, round_qk=False):
+        self.precise, self.round_qk = precise, round_qk
+        self.cd = torch.float32 if precise else torch.bfloat16          # "autocast" compute dtype
+
+    def lin(self, x, sd, name):
+        """nn.Linear under autocast: bf16 operands, bf16 out"""
+        b = sd.get(name + ".bias")
+        return F.linear(x.to(self.cd), sd[name + ".weight"].to(self.cd), None if b is None else b.to(self.cd))
+
+    def patch_embed(self, pixel_values, sd, ps):
+        """the patch Conv2d under autocast -> [B, P, C]"""
+        w, b = sd["embeddings.patch_embeddings.weight"].to(self.cd), sd["embeddings.patch_embeddings.bias"].to(self.cd)
+        return F.conv2d(pixel_values.float().to(self.cd), w, b, stride=ps).flatten(2).transpose(1, 2)
+
+    def varlen(self, q, k, v, cu):
+        """flash_attn_varlen_func on the windows [cu[i], cu[i+1]); rows in no window are 0"""
+        return varlen_attention(q, k, v, cu, cu, False, precise=self.precise)
 
 
-def lin(x, sd, name):
-    """nn.Linear under autocast: bf16 operands, bf16 out"""
-    b = sd.get(name + ".bias")
-    return F.linear(x.to(CD[0]), sd[name + ".weight"].to(CD[0]), None if b is None else b.to(CD[0]))
+BF16, PRECISE = Ops(), Ops(precise=True)
 
 
 def rope_cos_sin(gh, gw, head_dim, base):
@@ -90,64 +111,83 @@ def rotate_half(x):
     return torch.cat((-x2, x1), dim=-1)
 
 
-def rope_patches(t, cos, sin, n_prefix):
-    """apply_rotary_pos_emb (:216-246) on [B, H, S, D]: prefix tokens pass through (bf16), patch tokens rotate in fp32;
-    torch.cat promotes the result to fp32"""
-    pre, pat = t[..., :n_prefix, :], t[..., n_prefix:, :]
-    pat = (pat * cos) + (rotate_half(pat) * sin)
-    return torch.cat((pre, pat), dim=-2)
+def rope_rows(cos, sin, n_prefix, n_views):
+    """The [P, D] tables as one row per token of the flat [n_views * (n_prefix + P)] axis: identity rows (cos 1, sin 0) for the
+    prefix tokens.  apply_rotary_pos_emb (:216-246) lets the prefix tokens pass through and rotates the patch tokens;
+    t * 1 + rotate_half(t) * 0 is t, so one row-wise rotation with these tables gives the same values."""
+    D = cos.shape[1]
+    return (torch.cat([torch.ones(n_prefix, D), cos], 0).repeat(n_views, 1),
+            torch.cat([torch.zeros(n_prefix, D), sin], 0).repeat(n_views, 1))
 
 
-def embeddings(sd, cfg, pixel_values):
+def rope_apply(t, cos, sin):
+    """apply_rotary_pos_emb (:216-246) on [T, H, D] with per-row tables [T, D]: bf16 q/k rotate in fp32, the result is fp32"""
+    cos, sin = cos[:, None, :], sin[:, None, :]
+    return (t * cos) + (rotate_half(t) * sin)
+
+
+def embeddings(sd, cfg, pixel_values, ops=BF16):
     """DINOv3ViTEmbeddings.forward (:51-69): conv under autocast -> bf16, cls / registers fp32, cat -> fp32"""
-    ps = cfg["patch_size"]
-    w, b = sd["embeddings.patch_embeddings.weight"].to(CD[0]), sd["embeddings.patch_embeddings.bias"].to(CD[0])
-    pe = F.conv2d(pixel_values.float().to(CD[0]), w, b, stride=ps).flatten(2).transpose(1, 2)
+    pe = ops.patch_embed(pixel_values, sd, cfg["patch_size"])
     B = pixel_values.shape[0]
     return torch.cat([sd["embeddings.cls_token"].expand(B, -1, -1), sd["embeddings.register_tokens"].expand(B, -1, -1), pe], dim=1)
 
 
-def layer(sd, cfg, i, x, cos, sin, cu, B):
-    """DINOv3ViTLayer.forward (:407-439) with DINOv3ViTAttention.forward (:272-317) and the MLPs (:358-385)"""
+def layer(sd, cfg, i, x, cos, sin, cu, ops=BF16):
+    """DINOv3ViTLayer.forward (:407-439) with DINOv3ViTAttention.forward (:272-317) and the MLPs (:358-385) on flat token rows
+    x [T, C] with their RoPE rows cos / sin [T, D] (rope_rows).  Tokens meet only in the attention, whose windows `cu` are on
+    this row axis, so any run of rows stands for the reference's [B, S, C] batch."""
     C, nh = cfg["hidden_size"], cfg["num_attention_heads"]
     eps, p = cfg["layer_norm_eps"], f"layer.{i}."
-    S = x.shape[0] // B
+    T = x.shape[0]
     h = F.layer_norm(x.float(), (C,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], eps)
-    q = lin(h, sd, p + "attention.q_proj").view(B, S, nh, -1).transpose(1, 2)
-    k = lin(h, sd, p + "attention.k_proj").view(B, S, nh, -1).transpose(1, 2)
-    v = lin(h, sd, p + "attention.v_proj").view(B, S, nh, -1).transpose(1, 2)
-    n_prefix = S - cos.shape[0]
-    q, k = rope_patches(q, cos, sin, n_prefix), rope_patches(k, cos, sin, n_prefix)
-    q = q.transpose(1, 2).reshape(B * S, nh, -1)
-    k = k.transpose(1, 2).reshape(B * S, nh, -1)
-    v = v.transpose(1, 2).reshape(B * S, nh, -1)
-    ctx = varlen_attention(q, k, v, cu, cu, False).reshape(B * S, -1)         # fp32 in -> fp32 out (ref_shim convention)
-    a = lin(ctx, sd, p + "attention.o_proj")
+    q = ops.lin(h, sd, p + "attention.q_proj").view(T, nh, -1)
+    k = ops.lin(h, sd, p + "attention.k_proj").view(T, nh, -1)
+    v = ops.lin(h, sd, p + "attention.v_proj").view(T, nh, -1)
+    q, k = rope_apply(q, cos, sin), rope_apply(k, cos, sin)
+    if ops.round_qk:
+        q, k = q.to(torch.bfloat16).float(), k.to(torch.bfloat16).float()
+    ctx = ops.varlen(q, k, v, cu).reshape(T, -1)                              # fp32 in -> fp32 out (ref_shim convention)
+    a = ops.lin(ctx, sd, p + "attention.o_proj")
     x = a * sd[p + "layer_scale1.lambda1"] + x
     h = F.layer_norm(x.float(), (C,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], eps)
     if cfg["use_gated_mlp"]:
-        m = lin(F.silu(lin(h, sd, p + "mlp.gate_proj")) * lin(h, sd, p + "mlp.up_proj"), sd, p + "mlp.down_proj")
+        m = ops.lin(F.silu(ops.lin(h, sd, p + "mlp.gate_proj")) * ops.lin(h, sd, p + "mlp.up_proj"), sd, p + "mlp.down_proj")
     else:
-        m = lin(F.gelu(lin(h, sd, p + "mlp.up_proj")), sd, p + "mlp.down_proj")
+        m = ops.lin(F.gelu(ops.lin(h, sd, p + "mlp.up_proj")), sd, p + "mlp.down_proj")
     return m * sd[p + "layer_scale2.lambda1"] + x
 
 
-def forward(sd, cfg, pixel_values, cu_seqlens, num_layers=None, return_all=False, precise=False):
-    """DINOv3ViTModel.forward (:506-543) -> patch tokens fp32 [B, P, C]"""
-    if precise:
-        CD[0] = torch.float32
-        try:
-            return forward(sd, cfg, pixel_values, cu_seqlens, num_layers, return_all)
-        finally:
-            CD[0] = torch.bfloat16
+def final_norm(sd, cfg, x):
+    """the model's `norm` (:536-541) on every row"""
+    return F.layer_norm(x.float(), (cfg["hidden_size"],), sd["norm.weight"], sd["norm.bias"], cfg["layer_norm_eps"])
+
+
+def run_layers(sd, cfg, x, cos, sin, cu, num_layers=None, ops=BF16):
+    """`num_layers` layers and the final LayerNorm on flat token rows.  Returns (streams: the fp32 residual stream after each
+    layer, final LayerNorm of all T rows)."""
+    cu = [int(v) for v in (cu.tolist() if torch.is_tensor(cu) else cu)]
+    streams = []
+    for i in range(cfg["num_hidden_layers"] if num_layers is None else num_layers):
+        x = layer(sd, cfg, i, x, cos, sin, cu, ops)
+        streams.append(x)
+    return streams, final_norm(sd, cfg, x)
+
+
+def taps(sd, cfg, pixel_values, cu_seqlens, num_layers=None, ops=BF16):
+    """DINOv3ViTModel.forward (:506-543) with its intermediate results: dict(embed: the token matrix after `embeddings`
+    [B * S, C], streams: the residual stream after each layer, final_ln: the final LayerNorm of all B * S rows,
+    patch_tokens: what the reference returns, [B, P, C])."""
     ps, R = cfg["patch_size"], cfg["num_register_tokens"]
-    emb = embeddings(sd, cfg, pixel_values)
+    emb = embeddings(sd, cfg, pixel_values, ops)
     B, S, C = emb.shape
     gh, gw = pixel_values.shape[2] // ps, pixel_values.shape[3] // ps
-    cos, sin = rope_cos_sin(gh, gw, C // cfg["num_attention_heads"], cfg["rope_theta"])
+    cos, sin = rope_rows(*rope_cos_sin(gh, gw, C // cfg["num_attention_heads"], cfg["rope_theta"]), 1 + R, B)
     x = emb.reshape(B * S, C)
-    cu = [int(v) for v in (cu_seqlens.tolist() if torch.is_tensor(cu_seqlens) else cu_seqlens)]
-    for i in range(cfg["num_hidden_layers"] if num_layers is None else num_layers):
-        x = layer(sd, cfg, i, x, cos, sin, cu, B)
-    out = F.layer_norm(x.float(), (C,), sd["norm.weight"], sd["norm.bias"], cfg["layer_norm_eps"]).reshape(B, S, C)
-    return out[:, 1 + R:]
+    streams, out = run_layers(sd, cfg, x, cos, sin, cu_seqlens, num_layers, ops)
+    return dict(embed=x, streams=streams, final_ln=out, patch_tokens=out.reshape(B, S, C)[:, 1 + R:])
+
+
+def forward(sd, cfg, pixel_values, cu_seqlens, num_layers=None, precise=False):
+    """DINOv3ViTModel.forward (:506-543) -> patch tokens fp32 [B, P, C]; precise: fp32 Linears, fp64 attention (Ops)"""
+    return taps(sd, cfg, pixel_values, cu_seqlens, num_layers, PRECISE if precise else BF16)["patch_tokens"]

@@ -24,34 +24,6 @@ def rel(a, b):
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
-def precise_forward(sd, cfg, images, cu):
-    """the same network in fp32 weights / activations and fp64 attention: the yardstick both bf16 runs are measured against"""
-    C, nh, R, ps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["num_register_tokens"], cfg["patch_size"]
-    B = images.shape[0]
-    pe = F.conv2d(images.float(), sd["embeddings.patch_embeddings.weight"], sd["embeddings.patch_embeddings.bias"], stride=ps).flatten(2).transpose(1, 2)
-    x = torch.cat([sd["embeddings.cls_token"].expand(B, -1, -1), sd["embeddings.register_tokens"].expand(B, -1, -1), pe], 1)
-    S = x.shape[1]
-    x = x.reshape(B * S, C)
-    cos, sin = O3.rope_cos_sin(images.shape[2] // ps, images.shape[3] // ps, C // nh, cfg["rope_theta"])
-    lin = lambda t, n: F.linear(t, sd[n + ".weight"], sd.get(n + ".bias"))
-    from oracle.g2vlm_oracle import varlen_attention
-    for i in range(cfg["num_hidden_layers"]):
-        p = f"layer.{i}."
-        h = F.layer_norm(x, (C,), sd[p + "norm1.weight"], sd[p + "norm1.bias"], cfg["layer_norm_eps"])
-        q, k, v = (lin(h, p + f"attention.{n}_proj").view(B, S, nh, -1).transpose(1, 2) for n in "qkv")
-        q, k = O3.rope_patches(q, cos, sin, 1 + R), O3.rope_patches(k, cos, sin, 1 + R)
-        q, k, v = (t.transpose(1, 2).reshape(B * S, nh, -1) for t in (q, k, v))
-        ctx = varlen_attention(q, k, v, cu, cu, False, precise=True).reshape(B * S, -1)
-        x = lin(ctx, p + "attention.o_proj") * sd[p + "layer_scale1.lambda1"] + x
-        h = F.layer_norm(x, (C,), sd[p + "norm2.weight"], sd[p + "norm2.bias"], cfg["layer_norm_eps"])
-        if cfg["use_gated_mlp"]:
-            m = lin(F.silu(lin(h, p + "mlp.gate_proj")) * lin(h, p + "mlp.up_proj"), p + "mlp.down_proj")
-        else:
-            m = lin(F.gelu(lin(h, p + "mlp.up_proj")), p + "mlp.down_proj")
-        x = m * sd[p + "layer_scale2.lambda1"] + x
-    return F.layer_norm(x, (C,), sd["norm.weight"], sd["norm.bias"], cfg["layer_norm_eps"]).reshape(B, S, C)[:, 1 + R:]
-
-
 @pytest.mark.parametrize("name", ["dinov3_tiny", "dinov3_tiny_clean", "dinov3_tiny_r0", "dinov3_tiny_gated", "dinov3_real2"])
 def test_dinov3_matches_reference_golden(golden_dir, name):
     from g2vlm_amd.modeling.dinov3 import DINOv3ViTConfig, DINOv3ViTModel
@@ -66,7 +38,8 @@ def test_dinov3_matches_reference_golden(golden_dir, name):
     out = model(pixel_values=images, cu_seqlens=cu, max_seqlen=int((cu[1:] - cu[:-1]).max()))
     assert out.shape == ref.shape and out.dtype == torch.float32 and torch.isfinite(out).all()
     r = rel(out, ref)
-    prec = precise_forward(sd, cfg, images, meta["cu"])
+    # the same network in fp32 weights / activations and fp64 attention: the yardstick both bf16 runs are measured against
+    prec = O3.forward(sd, cfg, images, meta["cu"], precise=True)
     e_mine, e_ref = rel(out, prec), rel(ref, prec)
     print(name, f"rel vs golden {r:.3e}; vs full precision: engine {e_mine:.3e}, reference {e_ref:.3e}")
     assert r < 2e-2
