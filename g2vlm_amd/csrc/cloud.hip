@@ -14,13 +14,12 @@
 // stream (4 pixels = 3 vectors) wherever the address allows, and the components are picked out of the vectors.
 #include <float.h>
 
-#include "cloud_colour.h"                                   // cc_colour: the colour byte of a record, shared with render.hip
+#include "cloud_common.h"                                   // cc_colour, finite_f, the compaction's scan / count / flush, the checks
 #include "common.h"
 #include "g2vlm_hip.h"
 
 namespace {
 
-__device__ __forceinline__ bool finite_bits(uint32_t b) { return (b & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ bool nan_bits(uint32_t b) { return (b & 0x7fffffffu) > 0x7f800000u; }
 
 // ------------------------------------------------------------------------------------------------------------- mask
@@ -67,7 +66,7 @@ __global__ __launch_bounds__(CM_THREADS) void cloud_mask_kernel(const uint32_t* 
       const long p0 = view + (long)(r0 + i) * W + c0;
       // racing lanes all store the same 1
       cm_span(points, pvec != 0, total, p0 * 3, (p0 + cols) * 3, tid, [&](long d, uint32_t b) {
-        if (!finite_bits(b)) bad[i][(int)(d / 3 - p0)] = 1;
+        if (!finite_f(__uint_as_float(b))) bad[i][(int)(d / 3 - p0)] = 1;
       });
     }
   }
@@ -127,6 +126,7 @@ __global__ __launch_bounds__(CM_THREADS) void cloud_mask_kernel(const uint32_t* 
 // ---------------------------------------------------------------------------------------------------------- compaction
 constexpr int CC_THREADS = 256, CC_PER = 4, CC_BLOCK = CC_THREADS * CC_PER;   // pixels of one view per workgroup
 constexpr int CC_REC = 15;
+static_assert(CC_THREADS == PC_THREADS, "cloud_common.h's scan, count and flush are written for this workgroup");
 
 // the mask bytes of pixels [i, i + 4) of a view of hw pixels (pixels >= hw: 0), one dword where the address allows it
 __device__ __forceinline__ uint32_t cc_mask4(const uint8_t* m, long i, long hw) {
@@ -140,58 +140,20 @@ __device__ __forceinline__ uint32_t cc_mask4(const uint8_t* m, long i, long hw) 
 __device__ __forceinline__ int cc_kept(uint32_t w, int k) { return ((w >> (8 * k)) & 0xffu) != 0; }
 __device__ __forceinline__ int cc_count4(uint32_t w) { return cc_kept(w, 0) + cc_kept(w, 1) + cc_kept(w, 2) + cc_kept(w, 3); }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's CC_THREADS values; `total` is their sum.  sh: CC_THREADS / 64 ints.
-__device__ __forceinline__ int block_incl_scan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = wave_incl_scan(v, lane);
-  __syncthreads();                                           // sh may still be read from an earlier call
-  if (lane == 63) sh[wv] = v;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < CC_THREADS / 64; ++w) {
-    if (w < wv) before += sh[w];
-    total += sh[w];
-  }
-  return v + before;
-}
-
 // grid (blocks per view, N): kept pixels of the workgroup's CC_BLOCK pixels
 __global__ __launch_bounds__(CC_THREADS) void cloud_count_kernel(const uint8_t* mask, long hw, int* block_cnt) {
   __shared__ int sh[CC_THREADS / 64];
   const uint8_t* m = mask + (long)blockIdx.y * hw;
   const long i = (long)blockIdx.x * CC_BLOCK + threadIdx.x * CC_PER;
-  int c = cc_count4(cc_mask4(m, i, hw));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_cnt[(long)blockIdx.y * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  const int kept = block_sum(cc_count4(cc_mask4(m, i, hw)), sh);
+  if (threadIdx.x == 0) block_cnt[(long)blockIdx.y * gridDim.x + blockIdx.x] = kept;
 }
 
-// one workgroup: block_off[b] = kept pixels before block b (CC_THREADS blocks per pass, the running sum carried over),
-// counts[n] = kept pixels of view n.  The total is at most N H W <= 2^31 - 1.
+// one workgroup: block_off[b] = kept pixels before block b (block_offset_scan), counts[n] = kept pixels of view n.
+// The total is at most N H W <= 2^31 - 1.
 __global__ __launch_bounds__(CC_THREADS) void cloud_scan_kernel(const int* block_cnt, int* block_off, int* counts, int N, int bpv) {
   __shared__ int sh[CC_THREADS / 64];
-  const long nb = (long)N * bpv;
-  int carry = 0;
-  for (long b0 = 0; b0 < nb; b0 += CC_THREADS) {
-    const long b = b0 + threadIdx.x;
-    const int c = b < nb ? block_cnt[b] : 0;
-    int total;
-    const int incl = block_incl_scan(c, sh, total);
-    if (b < nb) block_off[b] = carry + incl - c;
-    carry += total;
-  }
+  block_offset_scan(block_cnt, block_off, (long)N * bpv, sh);
   for (int n = threadIdx.x; n < N; n += CC_THREADS) {
     int s = 0;
     for (int j = 0; j < bpv; ++j) s += block_cnt[(long)n * bpv + j];
@@ -199,8 +161,8 @@ __global__ __launch_bounds__(CC_THREADS) void cloud_scan_kernel(const int* block
   }
 }
 
-// grid (blocks per view, N).  The workgroup's records are staged in LDS at the byte offset its output range has inside a dword,
-// so that aligned dwords of LDS are aligned dwords of the output: head bytes, dwords, tail bytes.
+// grid (blocks per view, N).  The workgroup's records are staged in LDS at the byte offset its output range has inside a dword
+// and written out by staged_flush.
 __global__ __launch_bounds__(CC_THREADS) void cloud_scatter_kernel(const float* points, const float* colors, const uint8_t* mask,
                                                                     const int* block_off, uint8_t* rec, long max_records, long hw,
                                                                     int pvec, int cvec) {
@@ -260,17 +222,7 @@ __global__ __launch_bounds__(CC_THREADS) void cloud_scatter_kernel(const float* 
 
   long nrec = kept;                                          // records past the caller's capacity are not written
   if (first + nrec > max_records) nrec = max_records > first ? max_records - first : 0;
-  const int lo = mis, hi = mis + (int)nrec * CC_REC;         // stage bytes [lo, hi) go to out[lo, hi), out 4-byte aligned
-  uint8_t* out = rec + byte0 - mis;
-  const int dlo = (lo + 3) & ~3, dhi = hi & ~3;
-  if (dlo <= dhi) {
-    if (tid < dlo - lo) out[lo + tid] = stage[lo + tid];
-    for (int d = dlo + 4 * tid; d < dhi; d += 4 * CC_THREADS)
-      *reinterpret_cast<uint32_t*>(out + d) = *reinterpret_cast<const uint32_t*>(stage + d);
-    if (tid < hi - dhi) out[dhi + tid] = stage[dhi + tid];
-  } else {                                                   // fewer than 4 bytes inside one dword: never with 15-byte records
-    if (tid < hi - lo) out[lo + tid] = stage[lo + tid];
-  }
+  staged_flush(stage, rec, byte0, mis, (int)nrec * CC_REC);
 }
 
 inline int cc_blocks_per_view(int H, int W) { return (int)(((long)H * W + CC_BLOCK - 1) / CC_BLOCK); }
@@ -319,8 +271,7 @@ __global__ __launch_bounds__(CI_THREADS) void cloud_intrinsics_partial_kernel(co
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float X = xyz[3 * k], Y = xyz[3 * k + 1], Z = xyz[3 * k + 2];
-      const bool ok = i + k < hw && cc_kept(mw, k) && finite_bits(__float_as_uint(X)) && finite_bits(__float_as_uint(Y)) &&
-                      finite_bits(__float_as_uint(Z)) && Z > 0.f;
+      const bool ok = i + k < hw && cc_kept(mw, k) && finite_f(X) && finite_f(Y) && finite_f(Z) && Z > 0.f;
       if (!ok) continue;
       const long pix = i + k;
       const int y = (int)(pix / W), x = (int)(pix - (long)y * W);
@@ -367,41 +318,35 @@ __global__ __launch_bounds__(64) void cloud_intrinsics_solve_kernel(const double
   used[n] = (int)cnt;
 }
 
-inline bool bad_shape(int N, int H, int W) {
-  return N <= 0 || H <= 0 || W <= 0 || (int64_t)N * H * W > 0x7fffffffLL;
-}
-inline int aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-
 }  // namespace
 
 extern "C" int g2v_cloud_mask(const void* points, const void* local, const void* conf, int N, int H, int W, int flags, float conf_logit_min,
                               float edge_atol, float edge_rtol, void* mask, void* stream) {
   const int all = G2V_CLOUD_FINITE | G2V_CLOUD_CONF | G2V_CLOUD_EDGE_ATOL | G2V_CLOUD_EDGE_RTOL;
-  if (bad_shape(N, H, W) || (flags & ~all) || !mask) return G2V_ERR_ARG;
+  if (bad_nhw(N, H, W) || (flags & ~all) || !mask) return G2V_ERR_ARG;
   const bool edge = (flags & (G2V_CLOUD_EDGE_ATOL | G2V_CLOUD_EDGE_RTOL)) != 0;
   if (((flags & G2V_CLOUD_FINITE) && !points) || ((flags & G2V_CLOUD_CONF) && !conf) || (edge && !local)) return G2V_ERR_ARG;
-  if ((points && !aligned4(points)) || (local && !aligned4(local)) || (conf && !aligned4(conf))) return G2V_ERR_ARG;
+  if ((points && !aligned(points, 4)) || (local && !aligned(local, 4)) || (conf && !aligned(conf, 4))) return G2V_ERR_ARG;
   const dim3 grid((unsigned)((W + CM_TW - 1) / CM_TW), (unsigned)((H + CM_TH - 1) / CM_TH), (unsigned)N);
   if (grid.y > 65535u || grid.z > 65535u) return G2V_ERR_ARG;
   hipLaunchKernelGGL(cloud_mask_kernel, grid, dim3(CM_THREADS), 0, (hipStream_t)stream, (const uint32_t*)points, (const uint32_t*)local,
-                     (const float*)conf, (uint8_t*)mask, H, W, flags, conf_logit_min, edge_atol, edge_rtol, aligned16(points),
-                     aligned16(local));
+                     (const float*)conf, (uint8_t*)mask, H, W, flags, conf_logit_min, edge_atol, edge_rtol, aligned(points, 16),
+                     aligned(local, 16));
   G2V_CHECK_LAUNCH();
   return G2V_OK;
 }
 
 extern "C" int64_t g2v_cloud_compact_workspace(int N, int H, int W) {
-  if (bad_shape(N, H, W)) return 0;
+  if (bad_nhw(N, H, W)) return 0;
   return 8 * (int64_t)N * cc_blocks_per_view(H, W);
 }
 
 extern "C" int g2v_cloud_compact(const void* points, const void* colors, const void* mask, int N, int H, int W, void* records,
                                  int64_t max_records, void* counts, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (bad_shape(N, H, W) || !points || !colors || !mask || !counts || !workspace || max_records < 0 || (max_records > 0 && !records))
+  if (bad_nhw(N, H, W) || !points || !colors || !mask || !counts || !workspace || max_records < 0 || (max_records > 0 && !records))
     return G2V_ERR_ARG;
-  if (workspace_bytes < g2v_cloud_compact_workspace(N, H, W) || !aligned4(points) || !aligned4(colors) || !aligned4(workspace) ||
-      !aligned4(counts))
+  if (workspace_bytes < g2v_cloud_compact_workspace(N, H, W) || !aligned(points, 4) || !aligned(colors, 4) || !aligned(workspace, 4) ||
+      !aligned(counts, 4))
     return G2V_ERR_ARG;
   const int bpv = cc_blocks_per_view(H, W);
   if (N > 65535) return G2V_ERR_ARG;
@@ -415,26 +360,26 @@ extern "C" int g2v_cloud_compact(const void* points, const void* colors, const v
   G2V_CHECK_LAUNCH();
   if (max_records > 0) {
     hipLaunchKernelGGL(cloud_scatter_kernel, grid, dim3(CC_THREADS), 0, (hipStream_t)stream, (const float*)points, (const float*)colors,
-                       (const uint8_t*)mask, block_off, (uint8_t*)records, (long)max_records, hw, aligned16(points), aligned16(colors));
+                       (const uint8_t*)mask, block_off, (uint8_t*)records, (long)max_records, hw, aligned(points, 16), aligned(colors, 16));
     G2V_CHECK_LAUNCH();
   }
   return G2V_OK;
 }
 
 extern "C" int64_t g2v_intrinsics_lsq_workspace(int N, int H, int W) {
-  if (bad_shape(N, H, W)) return 0;
+  if (bad_nhw(N, H, W)) return 0;
   return 8 * (int64_t)CI_SUMS * N * ci_blocks_per_view(H, W);
 }
 
 extern "C" int g2v_intrinsics_lsq(const void* local, const void* mask, int N, int H, int W, void* K, void* used, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-  if (bad_shape(N, H, W) || !local || !K || !used || !workspace || N > 65535) return G2V_ERR_ARG;
-  if (workspace_bytes < g2v_intrinsics_lsq_workspace(N, H, W) || !aligned4(local) || !aligned4(K) || !aligned4(used) ||
-      (reinterpret_cast<uintptr_t>(workspace) & 7))
+  if (bad_nhw(N, H, W) || !local || !K || !used || !workspace || N > 65535) return G2V_ERR_ARG;
+  if (workspace_bytes < g2v_intrinsics_lsq_workspace(N, H, W) || !aligned(local, 4) || !aligned(K, 4) || !aligned(used, 4) ||
+      !aligned(workspace, 8))
     return G2V_ERR_ARG;
   const int bpv = ci_blocks_per_view(H, W);
   hipLaunchKernelGGL(cloud_intrinsics_partial_kernel, dim3((unsigned)bpv, (unsigned)N), dim3(CI_THREADS), 0, (hipStream_t)stream,
-                     (const float*)local, (const uint8_t*)mask, H, W, (double*)workspace, aligned16(local));
+                     (const float*)local, (const uint8_t*)mask, H, W, (double*)workspace, aligned(local, 16));
   G2V_CHECK_LAUNCH();
   hipLaunchKernelGGL(cloud_intrinsics_solve_kernel, dim3((unsigned)N), dim3(64), 0, (hipStream_t)stream, (const double*)workspace, bpv, H, W,
                      (float*)K, (int*)used);

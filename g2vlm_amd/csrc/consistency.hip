@@ -5,7 +5,8 @@
 // The rule (include/g2vlm_hip.h and DESIGN.md 6k state it in full): the world point P of a source pixel (i, p) is taken into
 // every other view j, q = R_j^T (P - t_j), u = fx q0/q2 + cx, v = fy q1/q2 + cy, and compared with the depth zt that j predicts
 // at the pixel (floor u, floor v): it agrees if |q2 - zt| <= rtol zt and lies in front if q2 - zt < -rtol zt.  Every operation
-// is an fp32 operation rounded once - contraction is switched off in project() - so that a numpy restatement gives the same bytes.
+// is an fp32 operation rounded once - contraction is switched off in cloud_common.h's to_camera, which render.hip projects with
+// too, and in project() - so that a numpy restatement gives the same bytes.
 //
 //   consistency_plane_kernel   the depth plane fp32 [N,H,W] in the workspace: local z where the mask keeps the pixel and z is
 //                              finite and > 0, NaN elsewhere (a NaN fails both compares, so the inner loop needs no validity
@@ -15,6 +16,7 @@
 //                              the chip reads one target's plane at a time.  The sixteen constants of a view are wave-uniform
 //                              loads.  pairs: ballot + popcount per wave, summed over the workgroup in LDS, one integer
 //                              atomicAdd per workgroup and (i, j, class) that is not zero; integer sums do not depend on order.
+#include "cloud_common.h"                                   // load_eligible, to_camera, finite_f, the entry point's checks
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -30,8 +32,6 @@ namespace {
 constexpr int CS_TW = G2V_CONSISTENCY_TILE_W, CS_TH = G2V_CONSISTENCY_TILE_H, CS_THREADS = CS_TW * CS_TH;
 constexpr int CS_MAX_VIEWS = 256, CP_THREADS = 256, CP_MAX_BLOCKS = 4096;
 static_assert(CS_THREADS == 256 && (CS_TW & (CS_TW - 1)) == 0, "a tile is 256 pixels, its width a power of two");
-
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
 // grid-stride over the N H W pixels and over the 2 N N pair counts
 __global__ __launch_bounds__(CP_THREADS) void consistency_plane_kernel(const float* local, const uint8_t* mask, float* plane, long total,
@@ -49,22 +49,17 @@ __global__ __launch_bounds__(CP_THREADS) void consistency_plane_kernel(const flo
 
 struct Cls { bool agree, front; };
 
-// One source point against one target view.  `c` = the view's constants {R row-major 9, t 3, fx, fy, cx, cy}.
-// Contraction off: every * and + below is its own rounding (v_mul_f32 / v_add_f32, never v_fma / v_fmac).
+// One source point against one target view: to_camera, then the depth the view predicts at the pixel the point lands on.
+// Contraction off: every * and - below is its own rounding.
 __device__ __forceinline__ Cls project(float px, float py, float pz, const float* __restrict__ pose, const float* __restrict__ k,
                                        const float* __restrict__ plane, int H, int W, float rtol) {
 #pragma clang fp contract(off)
-  const float d0 = px - pose[3], d1 = py - pose[7], d2 = pz - pose[11];
-  const float q0 = (pose[0] * d0 + pose[4] * d1) + pose[8] * d2;
-  const float q1 = (pose[1] * d0 + pose[5] * d1) + pose[9] * d2;
-  const float q2 = (pose[2] * d0 + pose[6] * d1) + pose[10] * d2;
-  const float u = k[0] * (q0 / q2) + k[2];                   // correctly rounded divisions: no fast-math in this build
-  const float v = k[4] * (q1 / q2) + k[5];
+  const CamPoint c = to_camera(px, py, pz, pose, k);
   Cls r = {false, false};
-  if (q2 > 0.f && u >= 0.f && u < (float)W && v >= 0.f && v < (float)H) {   // false on NaN; only inside is u or v converted
-    const int x = (int)u, y = (int)v;                        // 0 <= x < W, 0 <= y < H
+  if (c.q2 > 0.f && c.u >= 0.f && c.u < (float)W && c.v >= 0.f && c.v < (float)H) {   // false on NaN; only inside is u or v converted
+    const int x = (int)c.u, y = (int)c.v;                    // 0 <= x < W, 0 <= y < H
     const float zt = plane[(long)y * W + x];                 // finite and > 0, or NaN
-    const float tol = rtol * zt, diff = q2 - zt;
+    const float tol = rtol * zt, diff = c.q2 - zt;
     r.agree = fabsf(diff) <= tol;
     r.front = diff < -tol;
   }
@@ -85,10 +80,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_kernel(const float* __
   const long p = (long)i * hw + (long)y * W + x;
   float px = 0.f, py = 0.f, pz = 0.f;
   bool eligible = false;
-  if (live) {
-    px = points[p * 3]; py = points[p * 3 + 1]; pz = points[p * 3 + 2];
-    eligible = (!mask || mask[p] != 0) && finite_f(px) && finite_f(py) && finite_f(pz);
-  }
+  if (live) eligible = load_eligible(points, mask, p, px, py, pz);
   if (pairs) {
     for (int k = tid; k < 2 * N; k += CS_THREADS) sh_pairs[k] = 0;
     __syncthreads();
@@ -125,10 +117,7 @@ __global__ __launch_bounds__(CS_THREADS) void consistency_kernel(const float* __
 }
 
 // the tile rows of a view are the grid's y extent, which ends at 65535: H <= 65535 CS_TH
-inline bool bad_shape(int N, int H, int W) {
-  return N <= 0 || H <= 0 || W <= 0 || N > CS_MAX_VIEWS || H > 65535 * CS_TH || (int64_t)N * H * W > 0x7fffffffLL;
-}
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+inline bool bad_shape(int N, int H, int W) { return bad_nhw(N, H, W) || N > CS_MAX_VIEWS || H > 65535 * CS_TH; }
 
 }  // namespace
 
@@ -144,8 +133,8 @@ extern "C" int g2v_cloud_consistency(const void* points, const void* local, cons
   if (bad_shape(N, H, W) || !points || !local || !poses || !K || !workspace) return G2V_ERR_ARG;
   if (!(depth_rtol >= 0.f)) return G2V_ERR_ARG;              // negative or NaN
   if (!agree && !in_front && !pairs && !mask_out) return G2V_ERR_ARG;
-  if (workspace_bytes < g2v_cloud_consistency_workspace(N, H, W) || !aligned4(points) || !aligned4(local) || !aligned4(poses) ||
-      !aligned4(K) || !aligned4(workspace) || !aligned4(pairs))
+  if (workspace_bytes < g2v_cloud_consistency_workspace(N, H, W) || !aligned(points, 4) || !aligned(local, 4) || !aligned(poses, 4) ||
+      !aligned(K, 4) || !aligned(workspace, 4) || !aligned(pairs, 4))
     return G2V_ERR_ARG;
   const dim3 grid((unsigned)((W + CS_TW - 1) / CS_TW), (unsigned)((H + CS_TH - 1) / CS_TH), (unsigned)N);
   const long total = (long)N * H * W;

@@ -4,10 +4,10 @@
 // fp32 [N,H,W,3], a keep mask u8 [N,H,W] (NULL: all pixels) and an optional longest edge.
 //
 // The rule (include/g2vlm_hip.h and DESIGN.md 6n state it in full; tests/mesh_check.py restates it in numpy): a quad whose four
-// corners are kept is cut along its shorter diagonal (fp32 squared lengths, every operation rounded once - contraction is switched
-// off in classify() -, a tie or a NaN takes the main diagonal), a quad with three kept corners gives their one triangle, every
-// triangle faces the camera.  Faces come in view-major, quad row-major order; vertices are the kept pixels some face references, in
-// flat pixel order.  Every position is an integer prefix sum: the bytes do not depend on the order in which anything ran.
+// corners are kept is cut along its shorter diagonal (fp32 squared lengths by cloud_common.h's sq_dist3, every operation rounded
+// once - contraction is switched off there and in classify() -, a tie or a NaN takes the main diagonal), a quad with three kept
+// corners gives their one triangle, every triangle faces the camera.  Faces come in view-major, quad row-major order; vertices are
+// the kept pixels some face references, in flat pixel order.  Every position is an integer prefix sum: the bytes do not depend on the order in which anything ran.
 //
 //   mesh_classify_kernel   a workgroup per 32 x 8 tile of one view, the 9 x 33 points and mask bytes its quads touch in LDS (a
 //                          one-pixel halo to the right and below), one thread per quad: each quad is classified exactly once.
@@ -20,8 +20,9 @@
 //   mesh_vertex_kernel     vertex_of = block offset + rank inside the block, or -1.
 //   mesh_face_kernel       the faces of a block's quads: vertex ids of the corners through vertex_of, int32 triples stored
 //                          straight from registers (their slots are consecutive), the 13-byte PLY records staged in LDS at the
-//                          byte offset their range has inside a dword so that the stores are aligned dwords (cloud_scatter_kernel's
-//                          way with its 15-byte records).
+//                          byte offset their range has inside a dword so that the stores are aligned dwords (cloud_common.h's
+//                          staged_flush, as cloud_scatter_kernel's 15-byte records).
+#include "cloud_common.h"                                   // sq_dist3, the scan / count / flush of a block, the entry point's checks
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -30,6 +31,7 @@ namespace {
 constexpr int MT_TW = 32, MT_TH = 8, MT_THREADS = MT_TW * MT_TH;
 constexpr int MC_THREADS = 256, MC_PER = 4, MC_BLOCK = MC_THREADS * MC_PER;   // pixels of one view per workgroup
 constexpr int MF_REC = 13, MF_MAX = 2 * MC_BLOCK;                             // bytes of a face record, faces of a workgroup at most
+static_assert(MC_THREADS == PC_THREADS, "cloud_common.h's scan, count and flush are written for this workgroup");
 
 // triangle k of the quad with corners p00 p01 / p10 p11; bit k of a code byte.  0, 1: the anti diagonal's pair; 2, 3: the main one's
 enum { T_A1 = 1, T_A2 = 2, T_M1 = 4, T_M2 = 8 };               // (p00,p10,p01) (p01,p10,p11) (p00,p10,p11) (p00,p11,p01)
@@ -37,12 +39,7 @@ constexpr int USES_P00 = T_A1 | T_M1 | T_M2, USES_P01 = T_A1 | T_A2 | T_M2, USES
 
 struct P3 { float x, y, z; };
 
-// Contraction off: every - * + below is its own rounding (v_sub_f32 / v_mul_f32 / v_add_f32, never v_fma / v_fmac).
-__device__ __forceinline__ float edge2(P3 a, P3 b) {
-#pragma clang fp contract(off)
-  const float d0 = a.x - b.x, d1 = a.y - b.y, d2 = a.z - b.z;
-  return (d0 * d0 + d1 * d1) + d2 * d2;
-}
+__device__ __forceinline__ float edge2(P3 a, P3 b) { return sq_dist3(a.x, a.y, a.z, b.x, b.y, b.z); }
 
 // the code byte of one quad: k?? = the mask keeps the corner
 __device__ __forceinline__ int classify(P3 p00, P3 p01, P3 p10, P3 p11, bool k00, bool k01, bool k10, bool k11, bool stretch,
@@ -108,31 +105,6 @@ __global__ __launch_bounds__(MT_THREADS) void mesh_classify_kernel(const float* 
   code[base + (long)y * W + x] = (uint8_t)cd;
 }
 
-__device__ __forceinline__ int wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's MC_THREADS values; `total` is their sum.  sh: MC_THREADS / 64 ints.
-__device__ __forceinline__ int block_incl_scan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = wave_incl_scan(v, lane);
-  __syncthreads();                                           // sh may still be read from an earlier call
-  if (lane == 63) sh[wv] = v;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < MC_THREADS / 64; ++w) {
-    if (w < wv) before += sh[w];
-    total += sh[w];
-  }
-  return v + before;
-}
-
 // is pixel (y, x) of the view whose code bytes are `cv` a corner of some face?  Its four quads are anchored at (y, x), (y, x - 1),
 // (y - 1, x), (y - 1, x - 1); the code of a pixel in the last row or column is 0.
 __device__ __forceinline__ int used_of(const uint8_t* __restrict__ cv, int y, int x, int W) {
@@ -164,6 +136,9 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_count_kernel(const uint8_t* _
       if (++x == W) { x = 0; ++y; }
     }
   }
+  // Two sums in one butterfly and behind one barrier.  cloud_common.h's block_sum sums one value and has no barrier in front, so two
+  // calls would need a barrier more and run their butterflies one after the other: that form was +0.3 / +0.6 us on count_only
+  // (profiles/cloud_common_ab.json, "mesh_count_kernel_with_block_sum_twice"), so this kernel keeps the parent's code.
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     nv += __shfl_xor(nv, o, 64);
@@ -178,25 +153,14 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_count_kernel(const uint8_t* _
   }
 }
 
-// one workgroup: off[b] = the sum of cnt before block b (MC_THREADS blocks per pass, the running sum carried over), for the vertex and
-// the face counts in turn; counts[n] = {vertices, faces} of view n.  Both totals are at most 2^31 - 1 (the entry point's limits).
+// one workgroup: off[b] = the sum of cnt before block b (block_offset_scan), for the vertex and the face counts in turn;
+// counts[n] = {vertices, faces} of view n.  Both totals are at most 2^31 - 1 (the entry point's limits).
 __global__ __launch_bounds__(MC_THREADS) void mesh_scan_kernel(const int* cnt_v, const int* cnt_f, int* off_v, int* off_f, int* counts, int N,
                                                                 int bpv) {
   __shared__ int sh[MC_THREADS / 64];
   const long nb = (long)N * bpv;
-  for (int which = 0; which < 2; ++which) {
-    const int* cnt = which ? cnt_f : cnt_v;
-    int* off = which ? off_f : off_v;
-    int carry = 0;
-    for (long b0 = 0; b0 < nb; b0 += MC_THREADS) {
-      const long b = b0 + threadIdx.x;
-      const int c = b < nb ? cnt[b] : 0;
-      int total;
-      const int incl = block_incl_scan(c, sh, total);
-      if (b < nb) off[b] = carry + incl - c;
-      carry += total;
-    }
-  }
+  block_offset_scan(cnt_v, off_v, nb, sh);
+  block_offset_scan(cnt_f, off_f, nb, sh);
   for (int n = threadIdx.x; n < N; n += MC_THREADS) {
     int v = 0, f = 0;
     for (int j = 0; j < bpv; ++j) {
@@ -285,17 +249,7 @@ __global__ __launch_bounds__(MC_THREADS) void mesh_face_kernel(const uint8_t* __
 
   long nrec = nfaces;                                        // records past the caller's capacity are not written
   if (first + nrec > max_faces) nrec = max_faces > first ? max_faces - first : 0;
-  const int lo = mis, hi = mis + (int)nrec * MF_REC;         // stage bytes [lo, hi) go to out[lo, hi), out 4-byte aligned
-  uint8_t* out = rec + byte0 - mis;
-  const int dlo = (lo + 3) & ~3, dhi = hi & ~3;
-  if (dlo <= dhi) {
-    if (tid < dlo - lo) out[lo + tid] = stage[lo + tid];
-    for (int d = dlo + 4 * tid; d < dhi; d += 4 * MC_THREADS)
-      *reinterpret_cast<uint32_t*>(out + d) = *reinterpret_cast<const uint32_t*>(stage + d);
-    if (tid < hi - dhi) out[dhi + tid] = stage[dhi + tid];
-  } else {                                                   // fewer than 4 bytes inside one dword: never with 13-byte records
-    if (tid < hi - lo) out[lo + tid] = stage[lo + tid];
-  }
+  staged_flush(stage, rec, byte0, mis, (int)nrec * MF_REC);
 }
 
 inline int blocks_per_view(int H, int W) { return (int)(((long)H * W + MC_BLOCK - 1) / MC_BLOCK); }
@@ -303,10 +257,9 @@ inline int blocks_per_view(int H, int W) { return (int)(((long)H * W + MC_BLOCK 
 // N*H*W <= 2^31 - 1 keeps every vertex id in int32 (g2v_cloud_compact's limit), 2 N (H-1) (W-1) <= 2^31 - 1 every face count;
 // N is the grid's y extent
 inline bool bad_shape(int N, int H, int W) {
-  if (N <= 0 || H <= 0 || W <= 0 || N > 65535 || (int64_t)N * H * W > 0x7fffffffLL) return true;
+  if (bad_nhw(N, H, W) || N > 65535) return true;
   return 2 * (int64_t)N * (H - 1) * (W - 1) > 0x7fffffffLL;
 }
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
 struct Layout { int64_t cnt_v, cnt_f, off_v, off_f, vertex_of, code, used, bytes; };
 inline Layout layout(int N, int H, int W) {
@@ -332,8 +285,8 @@ extern "C" int g2v_cloud_mesh(const void* points, const void* mask, int N, int H
                               int64_t workspace_bytes, void* stream) {
   if (bad_shape(N, H, W) || !points || !counts || !workspace || (flags & ~G2V_MESH_MAX_EDGE) || max_faces < 0) return G2V_ERR_ARG;
   if ((flags & G2V_MESH_MAX_EDGE) && !(max_edge >= 0.f)) return G2V_ERR_ARG;   // negative or NaN
-  if (workspace_bytes < g2v_cloud_mesh_workspace(N, H, W) || !aligned4(points) || !aligned4(workspace) || !aligned4(counts) ||
-      !aligned4(vertex_of) || !aligned4(faces))
+  if (workspace_bytes < g2v_cloud_mesh_workspace(N, H, W) || !aligned(points, 4) || !aligned(workspace, 4) || !aligned(counts, 4) ||
+      !aligned(vertex_of, 4) || !aligned(faces, 4))
     return G2V_ERR_ARG;
   const Layout l = layout(N, H, W);
   uint8_t* ws = (uint8_t*)workspace;

@@ -3,14 +3,15 @@
 // [Nt,3], each with an optional u8 mask, and an optional largest distance.
 //
 // The rule (include/g2vlm_hip.h and DESIGN.md 6p state it in full; tests/nn_check.py restates it in numpy): a point takes part if
-// its mask byte is non-zero and its coordinates are finite; d = q - t, d2 = (d0 d0 + d1 d1) + d2 d2 in fp32, every operation rounded
-// once (contraction is off in this file); a target counts unless d2 > max_distance^2; the answer is the minimum of the 64-bit key
-// bits(d2) << 32 | index over the counting targets.  A minimum of integers does not depend on the order in which it is taken, so
+// its mask byte is non-zero and its coordinates are finite (cloud_common.h's load_eligible); d = q - t, d2 = (d0 d0 + d1 d1) + d2 d2
+// in fp32, every operation rounded once (cloud_common.h's sq_dist3, contraction off in its body as in this file); a target counts
+// unless d2 > max_distance^2; the answer is the minimum of the 64-bit key bits(d2) << 32 | index (dist_key) over the counting
+// targets.  A minimum of integers does not depend on the order in which it is taken, so
 // the search structure below is free to visit the targets in any order and to skip those that provably cannot hold the minimum.
 //
 //   nn_init_kernel      zeroes the stats and the bounds accumulators.
-//   nn_bounds_kernel    per-axis minimum and maximum of the participating targets and their number (voxel.hip's ordered-integer
-//                       atomics: order-free).
+//   nn_bounds_kernel    per-axis minimum and maximum of the participating targets and their number (cloud_common.h's
+//                       bounds_accumulate, as voxel.hip: ordered-integer atomics, order-free).
 //   nn_setup_kernel     one thread: the grid's origin, its cell width (cubic cells: the smallest width whose grid has at most C
 //                       cells, C = the largest cube <= 2 Nt, known on the host) and cells per axis from the bounds; stats[1].
 //   brute path          nn_keys_kernel fills the keys with EMPTY; nn_brute_kernel: a workgroup of 256 queries (one per lane, the
@@ -27,6 +28,7 @@
 // byte for byte; the outputs are, because the key minimum does not see that order.
 #include <math.h>
 
+#include "cloud_common.h"                                   // load_eligible, sq_dist3, dist_key, the bounds, the scan of a block
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -37,6 +39,7 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int NN_THREADS = 256;
+static_assert(NN_THREADS == PC_THREADS, "cloud_common.h's scan and bounds are written for this workgroup");
 constexpr int NN_TILE = 1024;                               // targets of one LDS tile of the brute path: 16 KiB
 constexpr long NN_BRUTE_PAIRS = 1L << 36;                   // pairs of one launch of the brute path at most: 26 ms at the measured rate
 constexpr int NN_SCAN_PER = 4, NN_SCAN_BLOCK = NN_THREADS * NN_SCAN_PER;   // cells per workgroup of the scan
@@ -62,27 +65,6 @@ struct Params {                                             // at the start of t
 };
 static_assert(sizeof(Params) <= NN_HEADER, "header");
 
-__device__ __forceinline__ bool nn_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ uint32_t nn_ord(float x) {       // order-preserving map of the finite floats onto unsigned integers
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float nn_unord(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// the rule's squared distance: v_sub / v_mul / v_add, each rounded once
-__device__ __forceinline__ float nn_d2(float qx, float qy, float qz, float tx, float ty, float tz) {
-#pragma clang fp contract(off)
-  const float dx = qx - tx, dy = qy - ty, dz = qz - tz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
-__device__ __forceinline__ u64 nn_key(float d2, int index) { return ((u64)__float_as_uint(d2) << 32) | (uint32_t)index; }
-
-__device__ __forceinline__ bool nn_takes_part(const float* __restrict__ p, const uint8_t* __restrict__ mask, long i, float& x, float& y,
-                                              float& z) {
-  x = p[3 * i]; y = p[3 * i + 1]; z = p[3 * i + 2];
-  return (!mask || mask[i] != 0) && nn_finite(x) && nn_finite(y) && nn_finite(z);
-}
-
 __global__ void nn_init_kernel(Params* P, int* stats) {
   const int t = threadIdx.x;
   if (t < 3) P->bounds[t] = 0xffffffffu;
@@ -92,36 +74,7 @@ __global__ void nn_init_kernel(Params* P, int* stats) {
 
 __global__ __launch_bounds__(NN_THREADS) void nn_bounds_kernel(const float* __restrict__ target, const uint8_t* __restrict__ mask, long Nt,
                                                                 Params* P) {
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  int cnt = 0;
-  for (long i = (long)blockIdx.x * NN_THREADS + threadIdx.x; i < Nt; i += (long)gridDim.x * NN_THREADS) {
-    float c[3];
-    if (!nn_takes_part(target, mask, i, c[0], c[1], c[2])) continue;
-    ++cnt;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t u = nn_ord(c[k]);
-      lo[k] = min(lo[k], u);
-      hi[k] = max(hi[k], u);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = min(lo[k], (uint32_t)__shfl_xor((int)lo[k], o, 64));
-      hi[k] = max(hi[k], (uint32_t)__shfl_xor((int)hi[k], o, 64));
-    }
-  }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      atomicMin(&P->bounds[k], lo[k]);
-      atomicMax(&P->bounds[3 + k], hi[k]);
-    }
-    atomicAdd(&P->bounds[6], (uint32_t)cnt);
-  }
+  bounds_accumulate(target, mask, Nt, P->bounds);
 }
 
 // cells along an axis of extent e under cell width w: the last one holds the maximum itself
@@ -137,7 +90,7 @@ __global__ void nn_setup_kernel(Params* P, long C, int* stats) {
   stats[1] = cnt;
   double ext[3], emax = 0.0;
   for (int k = 0; k < 3; ++k) {
-    const float lo = cnt ? nn_unord(P->bounds[k]) : 0.f, hi = cnt ? nn_unord(P->bounds[3 + k]) : 0.f;
+    const float lo = cnt ? float_unord(P->bounds[k]) : 0.f, hi = cnt ? float_unord(P->bounds[3 + k]) : 0.f;
     ext[k] = (double)hi - (double)lo;                       // finite: both are finite floats
     if (!(ext[k] > 0.0)) ext[k] = 0.0;
     emax = fmax(emax, ext[k]);
@@ -184,7 +137,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_brute_kernel(const float* __res
   __shared__ float4 tile[NN_TILE];
   const long q = (long)blockIdx.x * NN_THREADS + threadIdx.x;
   float qx = 0.f, qy = 0.f, qz = 0.f;
-  const bool part = q < Nq && nn_takes_part(query, qmask, q, qx, qy, qz);
+  const bool part = q < Nq && load_eligible(query, qmask, q, qx, qy, qz);
   u64 best = NN_EMPTY;
   const long t_begin = (tile0 + (long)blockIdx.y * tiles_per) * NN_TILE;
   long t_end = t_begin + tiles_per * NN_TILE;
@@ -195,7 +148,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_brute_kernel(const float* __res
     __syncthreads();                                         // the tile of the pass before has been read
     for (int j = threadIdx.x; j < n; j += NN_THREADS) {
       float x, y, z;
-      const bool ok = nn_takes_part(target, tmask, t0 + j, x, y, z);
+      const bool ok = load_eligible(target, tmask, t0 + j, x, y, z);
       tile[j] = make_float4(x, y, z, __int_as_float(ok ? (int)(t0 + j) : -1));
     }
     __syncthreads();
@@ -203,9 +156,9 @@ __global__ __launch_bounds__(NN_THREADS) void nn_brute_kernel(const float* __res
     for (int j = 0; j < n; ++j) {
       const float4 t = tile[j];                             // every lane reads the same address: a broadcast
       const int idx = __float_as_int(t.w);
-      const float d2 = nn_d2(qx, qy, qz, t.x, t.y, t.z);
+      const float d2 = sq_dist3(qx, qy, qz, t.x, t.y, t.z);
       if (idx >= 0 && d2 <= m2) {                           // d2 is never NaN for finite inputs; m2 = +inf: no limit
-        const u64 k = nn_key(d2, idx);
+        const u64 k = dist_key(d2, (uint32_t)idx);
         best = k < best ? k : best;
       }
     }
@@ -226,7 +179,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_cell_kernel(const float* __rest
   if (t >= Nt) return;
   float x, y, z;
   int cell = -1, r = 0;
-  if (nn_takes_part(target, tmask, t, x, y, z)) {
+  if (load_eligible(target, tmask, t, x, y, z)) {
     const int ix = nn_cell1(x, P->lo[0], P->inv[0], P->g[0]), iy = nn_cell1(y, P->lo[1], P->inv[1], P->g[1]),
               iz = nn_cell1(z, P->lo[2], P->inv[2], P->g[2]);
     cell = (iz * P->g[1] + iy) * P->g[0] + ix;              // < g0 g1 g2 <= C <= 2^24
@@ -234,31 +187,6 @@ __global__ __launch_bounds__(NN_THREADS) void nn_cell_kernel(const float* __rest
   }
   cell_of[t] = cell;
   rank[t] = r;
-}
-
-__device__ __forceinline__ int nn_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's NN_THREADS values; `total` is their sum.  sh: NN_THREADS / 64 ints.
-__device__ __forceinline__ int nn_block_incl_scan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = nn_wave_incl_scan(v, lane);
-  __syncthreads();                                           // sh may still be read from an earlier call
-  if (lane == 63) sh[wv] = v;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < NN_THREADS / 64; ++w) {
-    if (w < wv) before += sh[w];
-    total += sh[w];
-  }
-  return v + before;
 }
 
 // a[0..C) -> its exclusive scan inside every block of NN_SCAN_BLOCK cells; bsum[b] = the block's total
@@ -272,7 +200,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_scan_block_kernel(int* __restri
     c += v[k];
   }
   int total;
-  int run = nn_block_incl_scan(c, sh, total) - c;
+  int run = block_incl_scan(c, sh, total) - c;
 #pragma unroll
   for (int k = 0; k < NN_SCAN_PER; ++k) {
     if (i + k < C) a[i + k] = run;
@@ -281,18 +209,10 @@ __global__ __launch_bounds__(NN_THREADS) void nn_scan_block_kernel(int* __restri
   if (threadIdx.x == 0) bsum[blockIdx.x] = total;
 }
 
-// one workgroup: bsum -> its exclusive scan (NN_THREADS blocks per pass, the running sum carried over)
+// one workgroup: bsum -> its exclusive scan, in place (block_offset_scan)
 __global__ __launch_bounds__(NN_THREADS) void nn_scan_sums_kernel(int* bsum, long nb) {
   __shared__ int sh[NN_THREADS / 64];
-  int carry = 0;
-  for (long b0 = 0; b0 < nb; b0 += NN_THREADS) {
-    const long b = b0 + threadIdx.x;
-    const int c = b < nb ? bsum[b] : 0;
-    int total;
-    const int incl = nn_block_incl_scan(c, sh, total);
-    if (b < nb) bsum[b] = carry + incl - c;
-    carry += total;
-  }
+  block_offset_scan(bsum, bsum, nb, sh);
 }
 
 // start[c] += the sum of the blocks before its own; start[C] = the number of participating targets
@@ -321,9 +241,9 @@ __device__ __forceinline__ void nn_scan_range(const float4* __restrict__ sorted,
                                               u64& best) {
   for (int j = b; j < e; ++j) {
     const float4 t = sorted[j];
-    const float d2 = nn_d2(qx, qy, qz, t.x, t.y, t.z);
+    const float d2 = sq_dist3(qx, qy, qz, t.x, t.y, t.z);
     if (d2 <= m2) {
-      const u64 k = nn_key(d2, __float_as_int(t.w));
+      const u64 k = dist_key(d2, __float_as_uint(t.w));
       best = k < best ? k : best;
     }
   }
@@ -343,7 +263,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_query_kernel(const float* __res
   if (q >= Nq) return;
   float qx, qy, qz;
   u64 best = NN_EMPTY;
-  if (nn_takes_part(query, qmask, q, qx, qy, qz) && P->bounds[6] != 0) {
+  if (load_eligible(query, qmask, q, qx, qy, qz) && P->bounds[6] != 0) {
     const float qv[3] = {qx, qy, qz};
     int i0[3], g[3];
     double qc2 = 0.0;
@@ -380,8 +300,8 @@ __global__ __launch_bounds__(NN_THREADS) void nn_query_kernel(const float* __res
       const double bound = qc2 + B * B;
       if (!(bound > NN_TINY)) continue;
       const float bd = __uint_as_float((uint32_t)(best >> 32));
-      if (best != NN_EMPTY && nn_finite(bd) && (double)bd * NN_SAFE <= bound) break;
-      if (nn_finite(m2) && (double)m2 * NN_SAFE < bound) break;
+      if (best != NN_EMPTY && finite_f(bd) && (double)bd * NN_SAFE <= bound) break;
+      if (finite_f(m2) && (double)m2 * NN_SAFE < bound) break;
     }
   }
   keys[q] = best;
@@ -395,7 +315,7 @@ __global__ __launch_bounds__(NN_THREADS) void nn_finalize_kernel(const float* __
   int part = 0, none = 0;
   if (q < Nq) {
     float x, y, z;
-    part = nn_takes_part(query, qmask, q, x, y, z) ? 1 : 0;
+    part = load_eligible(query, qmask, q, x, y, z) ? 1 : 0;
     const u64 k = part ? keys[q] : NN_EMPTY;                // a query that takes no part: whatever the slot holds is not read
     const bool found = k != NN_EMPTY;
     none = part && !found;
@@ -439,7 +359,6 @@ inline Layout layout(int64_t Nq, int64_t Nt) {
 }
 
 inline bool bad_counts(int64_t Nq, int64_t Nt) { return Nq < 0 || Nt < 0 || Nq > 0x7fffffffLL || Nt > 0x7fffffffLL; }
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 inline unsigned blocks_of(long n, long per) { return (unsigned)((n + per - 1) / per); }
 
 }  // namespace

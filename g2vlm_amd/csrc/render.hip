@@ -3,10 +3,10 @@
 // batch entry - points fp32 [N,H,W,3], images fp32 [N,3,H,W], a keep mask - and the targets' camera-to-world poses fp32 [M,4,4]
 // and pinhole K fp32 [M,3,3]; outputs are a colour image, a depth map and the flat index of the source pixel, per target.
 //
-// The rule (include/g2vlm_hip.h and DESIGN.md 6l state it in full): q = R_m^T (P - t_m), u = fx q0/q2 + cx, v = fy q1/q2 + cy with
-// consistency.hip's arithmetic - fp32, every operation rounded once, contraction switched off - and the point lands on the pixel
-// ((int)u, (int)v) and on the (2 r + 1)^2 pixels around it, clipped.  A target pixel keeps the MINIMUM of the 64-bit keys
-// (bits of q2 << 32 | source index) of the points that cover it: for positive finite floats bit order is value order, so that is
+// The rule (include/g2vlm_hip.h and DESIGN.md 6l state it in full): q = R_m^T (P - t_m), u = fx q0/q2 + cx, v = fy q1/q2 + cy by
+// cloud_common.h's to_camera, as in consistency.hip - fp32, every operation rounded once, contraction switched off - and the point
+// lands on the pixel ((int)u, (int)v) and on the (2 r + 1)^2 pixels around it, clipped.  A target pixel keeps the MINIMUM of the
+// 64-bit keys (bits of q2 << 32 | source index: dist_key) of the points that cover it: for positive finite floats bit order is value order, so that is
 // the nearest point, the lower source index among equals; the keys are distinct and the minimum is associative, so the bytes do
 // not depend on the order in which anything ran.  tests/render_check.py restates the rule in numpy.
 //
@@ -19,7 +19,7 @@
 //                           an upper bound and a skip decided on it is still right.
 //   render_resolve_kernel   one thread per target pixel: the key's two words are depth and index, the colour is cc_colour of the
 //                           source pixel's three channels - the bytes the PLY export writes for it.
-#include "cloud_colour.h"
+#include "cloud_common.h"                                   // load_eligible, to_camera, dist_key, cc_colour, the entry point's checks
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -39,8 +39,6 @@ constexpr int RF_THREADS = 256, RF_MAX_BLOCKS = 8192;
 constexpr int R_MAX_RADIUS = 8, R_MAX_TARGETS = 65535;
 constexpr unsigned long long R_EMPTY = ~0ull;
 
-__device__ __forceinline__ bool finite_f(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 // grid-stride over the M OH OW keys
 __global__ __launch_bounds__(RF_THREADS) void render_fill_kernel(unsigned long long* keys, long total) {
   const long stride = (long)gridDim.x * RF_THREADS;
@@ -49,22 +47,16 @@ __global__ __launch_bounds__(RF_THREADS) void render_fill_kernel(unsigned long l
 
 struct Hit { bool lands; int x0, y0; float depth; };
 
-// One source point against one target camera: consistency.hip::project's arithmetic.  pose = the camera-to-world matrix row-major,
-// k = K row-major.  Contraction off: every * and + below is its own rounding (v_mul_f32 / v_add_f32, never v_fma / v_fmac).
+// One source point against one target camera: to_camera, then the pixel it lands on.
 __device__ __forceinline__ Hit project(float px, float py, float pz, const float* __restrict__ pose, const float* __restrict__ k,
                                        int OH, int OW) {
-#pragma clang fp contract(off)
-  const float d0 = px - pose[3], d1 = py - pose[7], d2 = pz - pose[11];
-  const float q0 = (pose[0] * d0 + pose[4] * d1) + pose[8] * d2;
-  const float q1 = (pose[1] * d0 + pose[5] * d1) + pose[9] * d2;
-  const float q2 = (pose[2] * d0 + pose[6] * d1) + pose[10] * d2;
-  const float u = k[0] * (q0 / q2) + k[2];                   // correctly rounded divisions: no fast-math in this build
-  const float v = k[4] * (q1 / q2) + k[5];
-  Hit h = {false, 0, 0, q2};
-  if (q2 > 0.f && finite_f(q2) && u >= 0.f && u < (float)OW && v >= 0.f && v < (float)OH) {   // false on NaN; only inside is u or v converted
+  const CamPoint c = to_camera(px, py, pz, pose, k);
+  Hit h = {false, 0, 0, c.q2};
+  // false on NaN; only inside is u or v converted
+  if (c.q2 > 0.f && finite_f(c.q2) && c.u >= 0.f && c.u < (float)OW && c.v >= 0.f && c.v < (float)OH) {
     h.lands = true;
-    h.x0 = (int)u;                                           // 0 <= x0 < OW, 0 <= y0 < OH
-    h.y0 = (int)v;
+    h.x0 = (int)c.u;                                         // 0 <= x0 < OW, 0 <= y0 < OH
+    h.y0 = (int)c.v;
   }
   return h;
 }
@@ -89,16 +81,13 @@ __global__ __launch_bounds__(RS_THREADS) void render_splat_kernel(const float* _
   const long p = (long)i * hw + (long)y * W + x;             // <= 2^31 - 1 where live
   float px = 0.f, py = 0.f, pz = 0.f;
   bool eligible = false;
-  if (x < W && y < H) {
-    px = points[p * 3]; py = points[p * 3 + 1]; pz = points[p * 3 + 2];
-    eligible = (!mask || mask[p] != 0) && finite_f(px) && finite_f(py) && finite_f(pz);
-  }
+  if (x < W && y < H) eligible = load_eligible(points, mask, p, px, py, pz);
   if (!eligible) return;                                     // a wave without an eligible pixel ends here as a whole
   for (int m = 0; m < M; ++m) {
     if (skip && skip[m] == i) continue;                      // wave-uniform
     const Hit h = project(px, py, pz, poses + (long)m * 16, K + (long)m * 9, OH, OW);
     if (!h.lands) continue;
-    const unsigned long long key = ((unsigned long long)__float_as_uint(h.depth) << 32) | (uint32_t)p;
+    const unsigned long long key = dist_key(h.depth, (uint32_t)p);
     unsigned long long* plane = keys + (long)m * ohw;
     const int xa = max(h.x0 - radius, 0), xb = min(h.x0 + radius, OW - 1);
     const int ya = max(h.y0 - radius, 0), yb = min(h.y0 + radius, OH - 1);
@@ -130,11 +119,7 @@ __global__ __launch_bounds__(RF_THREADS) void render_resolve_kernel(const unsign
   }
 }
 
-inline bool bad_target(int M, int OH, int OW) {
-  return M <= 0 || OH <= 0 || OW <= 0 || M > R_MAX_TARGETS || (int64_t)M * OH * OW > 0x7fffffffLL;
-}
-inline bool bad_source(int N, int H, int W) { return N <= 0 || H <= 0 || W <= 0 || (int64_t)N * H * W > 0x7fffffffLL; }
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+inline bool bad_target(int M, int OH, int OW) { return bad_nhw(M, OH, OW) || M > R_MAX_TARGETS; }
 
 }  // namespace
 
@@ -148,7 +133,7 @@ extern "C" int g2v_cloud_render(const void* points, const void* colors, const vo
                                 int radius, int background,
                                 void* color_out, void* depth_out, void* index_out,
                                 void* workspace, int64_t workspace_bytes, void* stream) {
-  if (bad_source(N, H, W) || bad_target(M, OH, OW) || !points || !poses || !K || !workspace) return G2V_ERR_ARG;
+  if (bad_nhw(N, H, W) || bad_target(M, OH, OW) || !points || !poses || !K || !workspace) return G2V_ERR_ARG;
   if (radius < 0 || radius > R_MAX_RADIUS || background < 0 || background > 0xFFFFFF) return G2V_ERR_ARG;
   if (!color_out && !depth_out && !index_out) return G2V_ERR_ARG;
   if (color_out && !colors) return G2V_ERR_ARG;

@@ -13,9 +13,13 @@
 //                      per cell writes the 15-byte PLY record.  Three launches: zero | accumulate | finalise.
 //
 // Every sum is an integer sum and every position an integer prefix sum: the bytes do not depend on the order in which anything ran.
-// All arithmetic on coordinates is fp64 without contraction, so that numpy computes the same bits.
+// All arithmetic on coordinates is fp64 without contraction, so that numpy computes the same bits: it stays in this file, under
+// the pragma below, which does not cover the header included above it.
 #include <math.h>
 
+// cloud_common.h: the bounds (bounds_accumulate reads a point before its mask byte, so voxel_bounds_kernel reads the points of
+// masked-out pixels too; voxel_insert_kernel tests the mask first and does not), finite_f, cc_colour, the scan and count of a block
+#include "cloud_common.h"
 #include "common.h"
 #include "g2vlm_hip.h"
 
@@ -30,7 +34,7 @@ constexpr int VX_REC = 15, VX_ACC = 8;                      // u64 per cell: n, 
 constexpr u64 VX_EMPTY = ~0ull;                             // a key has bit 63 clear
 constexpr double VX_Q = 16777216.0, VX_G = 1048576.0;       // 2^24 fraction steps per cell, cells [-2^20, 2^20) per axis
 
-__device__ __forceinline__ bool vx_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+static_assert(VX_THREADS == PC_THREADS, "cloud_common.h's scan, count and bounds are written for this workgroup");
 
 // the cell of a finite point: key = (gx + 2^20) | (gy + 2^20) << 21 | (gz + 2^20) << 42, q = round(2^24 (t - g)); false: out of range
 __device__ __forceinline__ bool vx_cell(const float p[3], double v, const double o[3], u64& key, uint32_t q[3]) {
@@ -58,84 +62,18 @@ __device__ __forceinline__ u64 vx_mix(u64 x) {              // splitmix64's fina
   return x ^ (x >> 31);
 }
 
-__device__ __forceinline__ uint8_t vx_colour(float c) {      // host.write_ply_binary: (uint8)(clip((double)c, 0, 1) * 255)
-  const double v = fmin(fmax((double)c, 0.0), 1.0) * 255.0;
-  return (uint8_t)(int)v;
-}
-
-__device__ __forceinline__ int vx_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-// inclusive scan over the workgroup's VX_THREADS values; `total` is their sum.  sh: VX_THREADS / 64 ints.
-__device__ __forceinline__ int vx_block_incl_scan(int v, int* sh, int& total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  v = vx_wave_incl_scan(v, lane);
-  __syncthreads();                                           // sh may still be read from an earlier call
-  if (lane == 63) sh[wv] = v;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int w = 0; w < VX_THREADS / 64; ++w) {
-    if (w < wv) before += sh[w];
-    total += sh[w];
-  }
-  return v + before;
-}
-
 // ---------------------------------------------------------------------------------------------------------------- bounds
-__device__ __forceinline__ uint32_t vx_ord(float x) {       // order-preserving map of the finite floats onto unsigned integers
-  const uint32_t u = __float_as_uint(x);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t vx_unord(uint32_t k) { return (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k; }
-
 __global__ void voxel_bounds_init_kernel(uint32_t* b) {
   if (threadIdx.x < 3) b[threadIdx.x] = 0xffffffffu;
   else if (threadIdx.x < 7) b[threadIdx.x] = 0u;
 }
 
 __global__ __launch_bounds__(VX_THREADS) void voxel_bounds_kernel(const float* points, const uint8_t* mask, long P, uint32_t* b) {
-  uint32_t lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-  int cnt = 0;
-  for (long p = (long)blockIdx.x * VX_THREADS + threadIdx.x; p < P; p += (long)gridDim.x * VX_THREADS) {
-    if (!mask[p]) continue;
-    const float c[3] = {points[3 * p], points[3 * p + 1], points[3 * p + 2]};
-    if (!(vx_finite(c[0]) && vx_finite(c[1]) && vx_finite(c[2]))) continue;
-    ++cnt;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const uint32_t u = vx_ord(c[k]);
-      lo[k] = min(lo[k], u);
-      hi[k] = max(hi[k], u);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    cnt += __shfl_xor(cnt, o, 64);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      lo[k] = min(lo[k], (uint32_t)__shfl_xor((int)lo[k], o, 64));
-      hi[k] = max(hi[k], (uint32_t)__shfl_xor((int)hi[k], o, 64));
-    }
-  }
-  if ((threadIdx.x & 63) == 0 && cnt) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      atomicMin(&b[k], lo[k]);
-      atomicMax(&b[3 + k], hi[k]);
-    }
-    atomicAdd(&b[6], (uint32_t)cnt);
-  }
+  bounds_accumulate(points, mask, P, b);                     // the entry point refuses a NULL mask
 }
 
 __global__ void voxel_bounds_decode_kernel(uint32_t* b) {
-  if (threadIdx.x < 6) b[threadIdx.x] = b[6] ? vx_unord(b[threadIdx.x]) : 0u;
+  if (threadIdx.x < 6) b[threadIdx.x] = b[6] ? __float_as_uint(float_unord(b[threadIdx.x])) : 0u;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- assign
@@ -153,9 +91,9 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_insert_kernel(const float* p
                                                                    uint8_t* flags, int* stats, u64 smask) {
   const long p = (long)blockIdx.x * VX_THREADS + threadIdx.x;
   bool part = false, out_of_range = false;
-  if (p < P && mask[p]) {
+  if (p < P && mask[p]) {                                    // the mask first: no point is read for a pixel it drops (load_eligible would)
     const float c[3] = {points[3 * p], points[3 * p + 1], points[3 * p + 2]};
-    if (vx_finite(c[0]) && vx_finite(c[1]) && vx_finite(c[2])) {
+    if (finite_f(c[0]) && finite_f(c[1]) && finite_f(c[2])) {
       const double o[3] = {ox, oy, oz};
       u64 key;
       uint32_t q[3];
@@ -208,26 +146,15 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_first_kernel(long P, const i
       ++c;
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) block_cnt[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+  c = block_sum(c, sh);
+  if (threadIdx.x == 0) block_cnt[blockIdx.x] = c;
 }
 
-// one workgroup: block_off[b] = first pixels before block b (VX_THREADS blocks per pass, the running sum carried over); stats[0] = M
+// one workgroup: block_off[b] = first pixels before block b (block_offset_scan); stats[0] = M
 __global__ __launch_bounds__(VX_THREADS) void voxel_scan_kernel(const int* block_cnt, int* block_off, long nb, int* stats) {
   __shared__ int sh[VX_THREADS / 64];
-  int carry = 0;
-  for (long b0 = 0; b0 < nb; b0 += VX_THREADS) {
-    const long b = b0 + threadIdx.x;
-    const int c = b < nb ? block_cnt[b] : 0;
-    int total;
-    const int incl = vx_block_incl_scan(c, sh, total);
-    if (b < nb) block_off[b] = carry + incl - c;
-    carry += total;
-  }
-  if (threadIdx.x == 0) stats[0] = carry;
+  const int cells = block_offset_scan(block_cnt, block_off, nb, sh);
+  if (threadIdx.x == 0) stats[0] = cells;
 }
 
 // grid ceil(P / VX_BLOCK): the first pixel of a cell writes the cell's dense id, its rank among the first pixels
@@ -242,7 +169,7 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_rank_kernel(long P, const ui
     c += f[k];
   }
   int total;
-  int rank = block_off[blockIdx.x] + vx_block_incl_scan(c, sh, total) - c;
+  int rank = block_off[blockIdx.x] + block_incl_scan(c, sh, total) - c;
 #pragma unroll
   for (int k = 0; k < VX_PER; ++k)
     if (f[k]) voxel_of[i + k] = rank++;
@@ -282,8 +209,8 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_accumulate_kernel(const floa
     const double o[3] = {ox, oy, oz};
     if (vx_cell(c, v, o, key, val)) {
       const long n = p / hw, i = p - n * hw;
-      const uint32_t r = vx_colour(colors[(n * 3 + 0) * hw + i]), g = vx_colour(colors[(n * 3 + 1) * hw + i]),
-                     b = vx_colour(colors[(n * 3 + 2) * hw + i]);
+      const uint32_t r = cc_colour(colors[(n * 3 + 0) * hw + i]), g = cc_colour(colors[(n * 3 + 1) * hw + i]),
+                     b = cc_colour(colors[(n * 3 + 2) * hw + i]);
       val[3] = 1u | (r << 8);
       val[4] = g | (b << 16);
     } else {
@@ -349,11 +276,9 @@ __global__ __launch_bounds__(VX_THREADS) void voxel_finalize_kernel(const u64* a
   counts[m] = (int)n;
 }
 
-inline bool bad_shape(int N, int H, int W) { return N <= 0 || H <= 0 || W <= 0 || (int64_t)N * H * W > 0x7fffffffLL; }
 inline bool bad_grid(double v, double ox, double oy, double oz) {
   return !(v > 0.0) || !isfinite(v) || !isfinite(ox) || !isfinite(oy) || !isfinite(oz);
 }
-inline bool aligned(const void* p, int a) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(a - 1)) == 0; }
 inline int64_t vx_slots(int64_t P) {                         // the power of two >= 2 P: the load never exceeds 0.5
   int64_t s = 2;
   while (s < 2 * P) s <<= 1;
@@ -368,7 +293,7 @@ inline unsigned vx_grid(int64_t items) {                     // grid of a grid-s
 }  // namespace
 
 extern "C" int g2v_voxel_bounds(const void* points, const void* mask, int N, int H, int W, void* bounds, void* stream) {
-  if (bad_shape(N, H, W) || !points || !mask || !bounds || !aligned(points, 4) || !aligned(bounds, 4)) return G2V_ERR_ARG;
+  if (bad_nhw(N, H, W) || !points || !mask || !bounds || !aligned(points, 4) || !aligned(bounds, 4)) return G2V_ERR_ARG;
   const long P = (long)N * H * W;
   hipLaunchKernelGGL(voxel_bounds_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (uint32_t*)bounds);
   G2V_CHECK_LAUNCH();
@@ -381,7 +306,7 @@ extern "C" int g2v_voxel_bounds(const void* points, const void* mask, int N, int
 }
 
 extern "C" int64_t g2v_voxel_assign_workspace(int N, int H, int W) {
-  if (bad_shape(N, H, W)) return 0;
+  if (bad_nhw(N, H, W)) return 0;
   const int64_t P = (int64_t)N * H * W;
   return 12 * vx_slots(P) + 4 * P + 8 * vx_blocks(P) + P;    // keys u64, first i32 | slot_of u32 | block counts, offsets | flags u8
 }
@@ -389,7 +314,7 @@ extern "C" int64_t g2v_voxel_assign_workspace(int N, int H, int W) {
 extern "C" int g2v_voxel_assign(const void* points, const void* mask, int N, int H, int W, double voxel_size, double origin_x,
                                 double origin_y, double origin_z, void* voxel_of, void* stats, void* workspace,
                                 int64_t workspace_bytes, void* stream) {
-  if (bad_shape(N, H, W) || !points || !mask || !voxel_of || !stats || !workspace || bad_grid(voxel_size, origin_x, origin_y, origin_z))
+  if (bad_nhw(N, H, W) || !points || !mask || !voxel_of || !stats || !workspace || bad_grid(voxel_size, origin_x, origin_y, origin_z))
     return G2V_ERR_ARG;
   if (workspace_bytes < g2v_voxel_assign_workspace(N, H, W) || !aligned(points, 4) || !aligned(voxel_of, 4) || !aligned(stats, 4) ||
       !aligned(workspace, 8))
@@ -429,7 +354,7 @@ extern "C" int64_t g2v_voxel_reduce_workspace(int64_t M) {
 extern "C" int g2v_voxel_reduce(const void* points, const void* colors, const void* voxel_of, int N, int H, int W, double voxel_size,
                                 double origin_x, double origin_y, double origin_z, int64_t M, void* records, void* counts,
                                 void* out_points, void* out_colors, void* workspace, int64_t workspace_bytes, int flags, void* stream) {
-  if (bad_shape(N, H, W) || !points || !colors || !voxel_of || bad_grid(voxel_size, origin_x, origin_y, origin_z) || M < 0 ||
+  if (bad_nhw(N, H, W) || !points || !colors || !voxel_of || bad_grid(voxel_size, origin_x, origin_y, origin_z) || M < 0 ||
       M > (int64_t)N * H * W || (flags & ~G2V_VOXEL_NO_RUNS))
     return G2V_ERR_ARG;
   if (!aligned(points, 4) || !aligned(colors, 4) || !aligned(voxel_of, 4)) return G2V_ERR_ARG;

@@ -958,9 +958,32 @@ def _cloud_workspace(nbytes, device, tag):
     return ws
 
 
+def _workspace_arg(workspace, nbytes, device, tag):
+    """(workspace, the bytes to pass for it): the caller's own, or the scratch owner's buffer for `tag`, grown to nbytes."""
+    if workspace is None:
+        workspace = _cloud_workspace(nbytes, device, tag)
+    return workspace, workspace.numel() * workspace.element_size()
+
+
 def _nhw3(t, what):
     assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.shape[3] == 3 and t.is_contiguous(), f"{what}: fp32 [N,H,W,3], contiguous"
     return tuple(t.shape[:3])
+
+
+def _mask_u8(mask, shape, what="mask", optional=False):
+    """mask as uint8 of `shape` (a bool mask is viewed, not copied); None passes where optional (all pixels / points)."""
+    if mask is None and optional:
+        return None
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    dims = "[N,H,W]" if len(shape) == 3 else str(list(shape))
+    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == tuple(shape) and mask.is_contiguous(), f"{what}: uint8 {dims}"
+    return mask
+
+
+def _colors_n3hw(colors, N, H, W):
+    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
+        "colors: fp32 [N,3,H,W], contiguous"
 
 
 def cloud_mask(points=None, local=None, conf=None, conf_logit_min=0.0, edge_atol=None, edge_rtol=None, finite=True, out=None):
@@ -1000,19 +1023,14 @@ def cloud_compact(points, colors, mask, workspace=None):
     mask uint8 or bool [N,H,W] -> (records uint8 [M,15] = <f4 x,y,z + u1 r,g,b in view-major, row-major order, counts int32
     [N]).  Synchronous: the total M is read back once to size the result (a view of a buffer of N*H*W records)."""
     N, H, W = _nhw3(points, "points")
-    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
-        "colors: fp32 [N,3,H,W], contiguous"
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
-    nbytes = cloud_compact_workspace(N, H, W)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, points.device, "compact")
+    _colors_n3hw(colors, N, H, W)
+    mask = _mask_u8(mask, (N, H, W))
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_compact_workspace(N, H, W), points.device, "compact")
     cap = N * H * W
     records = torch.empty((cap, 15), dtype=torch.uint8, device=points.device)
     counts = torch.empty(N, dtype=torch.int32, device=points.device)
     _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(mask), N, H, W, _p(records), cap, _p(counts), _p(workspace),
-                                workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_compact")
+                                ws_bytes, _stream()), "g2v_cloud_compact")
     m = int(counts.sum(dtype=torch.int64).item())
     return records[:m], counts
 
@@ -1020,12 +1038,11 @@ def cloud_compact(points, colors, mask, workspace=None):
 def cloud_counts(points, colors, mask, workspace=None):
     """counts int32 [N] of cloud_compact alone: g2v_cloud_compact with room for no record (it then only counts)."""
     N, H, W = _nhw3(points, "points")
-    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
-    if workspace is None:
-        workspace = _cloud_workspace(cloud_compact_workspace(N, H, W), points.device, "compact")
+    mask = _mask_u8(mask, (N, H, W))
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_compact_workspace(N, H, W), points.device, "compact")
     counts = torch.empty(N, dtype=torch.int32, device=points.device)
     _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(mask), N, H, W, None, 0, _p(counts), _p(workspace),
-                                workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_compact")
+                                ws_bytes, _stream()), "g2v_cloud_compact")
     return counts
 
 
@@ -1038,17 +1055,11 @@ def intrinsics_lsq(local, mask=None, workspace=None):
     v = fy Y/Z + cy over pixel centres (x + 0.5, y + 0.5) and the pixels mask keeps (None: all) with finite X, Y, Z and Z > 0.
     Returns (K fp32 [N,3,3], used int32 [N]); entries that the pixels do not determine are NaN.  Bit-reproducible."""
     N, H, W = _nhw3(local, "local")
-    if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
-    nbytes = intrinsics_lsq_workspace(N, H, W)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, local.device, "intrinsics")
+    mask = _mask_u8(mask, (N, H, W), optional=True)
+    workspace, ws_bytes = _workspace_arg(workspace, intrinsics_lsq_workspace(N, H, W), local.device, "intrinsics")
     K = torch.empty((N, 3, 3), dtype=torch.float32, device=local.device)
     used = torch.empty(N, dtype=torch.int32, device=local.device)
-    _ck(lib().g2v_intrinsics_lsq(_p(local), _p(mask), N, H, W, _p(K), _p(used), _p(workspace),
-                                 workspace.numel() * workspace.element_size(), _stream()), "g2v_intrinsics_lsq")
+    _ck(lib().g2v_intrinsics_lsq(_p(local), _p(mask), N, H, W, _p(K), _p(used), _p(workspace), ws_bytes, _stream()), "g2v_intrinsics_lsq")
     return K, used
 
 
@@ -1064,23 +1075,18 @@ def cloud_consistency(points, local, mask, poses, K, depth_rtol, min_agree=0, ma
     None).  Bit-reproducible; no host synchronisation."""
     N, H, W = _nhw3(points, "points")
     assert _nhw3(local, "local") == (N, H, W), "local: the shape of points"
-    if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    mask = _mask_u8(mask, (N, H, W), optional=True)
     for t, shape, what in ((poses, (N, 4, 4), "poses"), (K, (N, 3, 3), "K")):
         assert t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == shape and t.is_contiguous(), f"{what}: fp32 {list(shape)}, contiguous"
     dev = points.device
-    nbytes = cloud_consistency_workspace(N, H, W)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, dev, "consistency")
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_consistency_workspace(N, H, W), dev, "consistency")
     agree = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
     in_front = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
     mask_out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
     pair_counts = torch.empty((N, N, 2), dtype=torch.int32, device=dev) if pairs else None
     _ck(lib().g2v_cloud_consistency(_p(points), _p(local), _p(mask), _p(poses), _p(K), N, H, W, float(depth_rtol), int(min_agree),
                                     int(max_in_front), _p(agree), _p(in_front), _p(pair_counts), _p(mask_out), _p(workspace),
-                                    workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_consistency")
+                                    ws_bytes, _stream()), "g2v_cloud_consistency")
     return agree, in_front, mask_out, pair_counts
 
 
@@ -1099,12 +1105,8 @@ def cloud_render(points, colors, mask, poses, K, size, radius=0, background=0, s
     Bit-reproducible; no host synchronisation."""
     N, H, W = _nhw3(points, "points")
     if colors is not None:
-        assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
-            "colors: fp32 [N,3,H,W], contiguous"
-    if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+        _colors_n3hw(colors, N, H, W)
+    mask = _mask_u8(mask, (N, H, W), optional=True)
     assert poses.dim() == 3, "poses: fp32 [M,4,4]"
     M, (OH, OW) = poses.shape[0], size
     for t, shape, what in ((poses, (M, 4, 4), "poses"), (K, (M, 3, 3), "K")):
@@ -1112,15 +1114,13 @@ def cloud_render(points, colors, mask, poses, K, size, radius=0, background=0, s
     if skip is not None:
         assert skip.is_cuda and skip.dtype == torch.int32 and tuple(skip.shape) == (M,) and skip.is_contiguous(), "skip: int32 [M]"
     dev = points.device
-    nbytes = cloud_render_workspace(M, OH, OW)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, dev, "render")
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_render_workspace(M, OH, OW), dev, "render")
     color_out = torch.empty((M, OH, OW, 3), dtype=torch.uint8, device=dev) if color else None
     depth_out = torch.empty((M, OH, OW), dtype=torch.float32, device=dev) if depth else None
     index_out = torch.empty((M, OH, OW), dtype=torch.int32, device=dev) if index else None
     _ck(lib().g2v_cloud_render(_p(points), _p(colors), _p(mask), N, H, W, _p(poses), _p(K), _p(skip), M, int(OH), int(OW), int(radius),
                                int(background), _p(color_out), _p(depth_out), _p(index_out), _p(workspace),
-                               workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_render")
+                               ws_bytes, _stream()), "g2v_cloud_render")
     return color_out, depth_out, index_out
 
 
@@ -1137,10 +1137,7 @@ def cloud_mesh_raw(points, mask, max_edge, counts, used=None, vertex_of=None, fa
     counts int32 [N,2] always; used uint8 [N,H,W], vertex_of int32 [N,H,W], faces int32 [cap,3], face_records uint8 [cap,13] where
     given - the capacity is that of the face tensors (0 without them: the call then only counts)."""
     N, H, W = _nhw3(points, "points")
-    if mask is not None:
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-        assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
+    mask = _mask_u8(mask, (N, H, W), optional=True)
     assert counts.is_cuda and counts.dtype == torch.int32 and tuple(counts.shape) == (N, 2) and counts.is_contiguous(), "counts: int32 [N,2]"
     for t, dtype, what in ((used, torch.uint8, "used"), (vertex_of, torch.int32, "vertex_of")):
         assert t is None or (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (N, H, W) and t.is_contiguous()), f"{what}: {dtype} [N,H,W]"
@@ -1150,12 +1147,10 @@ def cloud_mesh_raw(points, mask, max_edge, counts, used=None, vertex_of=None, fa
             assert t.is_cuda and t.dtype == dtype and t.dim() == 2 and t.shape[1] == width and t.is_contiguous(), f"{what}: {dtype} [cap,{width}]"
             assert cap is None or cap == t.shape[0], "faces and face_records: one capacity"
             cap = t.shape[0]
-    nbytes = cloud_mesh_workspace(N, H, W)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, points.device, "mesh")
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_mesh_workspace(N, H, W), points.device, "mesh")
     _ck(lib().g2v_cloud_mesh(_p(points), _p(mask), N, H, W, MESH_MAX_EDGE if max_edge is not None else 0, float(max_edge or 0.0), _p(used),
                              _p(vertex_of), _p(faces) if cap else None, _p(face_records) if cap else None, int(cap or 0), _p(counts),
-                             _p(workspace), workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_mesh")
+                             _p(workspace), ws_bytes, _stream()), "g2v_cloud_mesh")
 
 
 def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=True, workspace=None):
@@ -1167,8 +1162,7 @@ def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=Tru
     worst case is 25 bytes for each of 2 N (H-1) (W-1) candidates).  Synchronous: counts are read back once, and
     size the vertex records as well."""
     N, H, W = _nhw3(points, "points")
-    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
-        "colors: fp32 [N,3,H,W], contiguous"
+    _colors_n3hw(colors, N, H, W)
     dev = points.device
     counts = torch.empty((N, 2), dtype=torch.int32, device=dev)
     cloud_mesh_raw(points, mask, max_edge, counts, workspace=workspace)
@@ -1180,9 +1174,9 @@ def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=Tru
     cloud_mesh_raw(points, mask, max_edge, counts, used, vertex_of, f, fr, workspace=workspace)
     vertex_records = torch.empty((nv, 15), dtype=torch.uint8, device=dev)
     per_view = torch.empty(N, dtype=torch.int32, device=dev)
-    ws = _cloud_workspace(cloud_compact_workspace(N, H, W), dev, "compact")
+    ws, ws_bytes = _workspace_arg(None, cloud_compact_workspace(N, H, W), dev, "compact")
     _ck(lib().g2v_cloud_compact(_p(points), _p(colors), _p(used), N, H, W, _p(vertex_records) if nv else None, nv, _p(per_view), _p(ws),
-                                ws.numel() * ws.element_size(), _stream()), "g2v_cloud_compact")
+                                ws_bytes, _stream()), "g2v_cloud_compact")
     return dict(vertex_records=vertex_records, faces=f, face_records=fr, used=used, vertex_of=vertex_of, counts=counts)
 
 
@@ -1199,24 +1193,16 @@ def cloud_nn_raw(query, query_mask, target, target_mask, max_distance, flags, in
     for t, what in ((query, "query"), (target, "target")):
         assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous(), f"{what}: fp32 [N,3], contiguous"
     Nq, Nt = query.shape[0], target.shape[0]
-    masks = []
-    for m, n, what in ((query_mask, Nq, "query_mask"), (target_mask, Nt, "target_mask")):
-        if m is not None:
-            if m.dtype == torch.bool:
-                m = m.view(torch.uint8)
-            assert m.is_cuda and m.dtype == torch.uint8 and tuple(m.shape) == (n,) and m.is_contiguous(), f"{what}: uint8 [{n}]"
-        masks.append(m)
+    masks = [_mask_u8(query_mask, (Nq,), "query_mask", optional=True), _mask_u8(target_mask, (Nt,), "target_mask", optional=True)]
     assert index.is_cuda and index.dtype == torch.int32 and tuple(index.shape) == (Nq,) and index.is_contiguous(), "index: int32 [Nq]"
     assert sq_distance.is_cuda and sq_distance.dtype == torch.float32 and tuple(sq_distance.shape) == (Nq,) and sq_distance.is_contiguous(), \
         "sq_distance: fp32 [Nq]"
     assert stats.is_cuda and stats.dtype == torch.int32 and tuple(stats.shape) == (4,), "stats: int32 [4]"
-    nbytes = cloud_nn_workspace(Nq, Nt)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, query.device, "nn")
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_nn_workspace(Nq, Nt), query.device, "nn")
     _ck(lib().g2v_cloud_nn(_p(query) if Nq else None, _p(masks[0]) if Nq else None, Nq, _p(target) if Nt else None,
                            _p(masks[1]) if Nt else None, Nt, float("inf") if max_distance is None else float(max_distance), int(flags),
                            _p(index) if Nq else None, _p(sq_distance) if Nq else None, _p(stats), _p(workspace),
-                           workspace.numel() * workspace.element_size(), _stream()), "g2v_cloud_nn")
+                           ws_bytes, _stream()), "g2v_cloud_nn")
 
 
 def cloud_nn(query, target, max_distance=None, query_mask=None, target_mask=None, flags=0, workspace=None):
@@ -1239,10 +1225,7 @@ VOXEL_NO_RUNS = 1                                          # G2V_VOXEL_NO_RUNS (
 
 def _voxel_inputs(points, mask):
     N, H, W = _nhw3(points, "points")
-    if mask.dtype == torch.bool:
-        mask = mask.view(torch.uint8)
-    assert mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (N, H, W) and mask.is_contiguous(), "mask: uint8 [N,H,W]"
-    return N, H, W, mask
+    return N, H, W, _mask_u8(mask, (N, H, W))
 
 
 def voxel_bounds(points, mask):
@@ -1271,13 +1254,11 @@ def voxel_assign(points, mask, voxel_size, origin, workspace=None):
     Synchronous: the four stats are read back once."""
     N, H, W, mask = _voxel_inputs(points, mask)
     ox, oy, oz = (float(o) for o in origin)
-    nbytes = voxel_assign_workspace(N, H, W)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, points.device, "voxel_assign")
+    workspace, ws_bytes = _workspace_arg(workspace, voxel_assign_workspace(N, H, W), points.device, "voxel_assign")
     voxel_of = torch.empty((N, H, W), dtype=torch.int32, device=points.device)
     stats = torch.empty(4, dtype=torch.int32, device=points.device)
     _ck(lib().g2v_voxel_assign(_p(points), _p(mask), N, H, W, float(voxel_size), ox, oy, oz, _p(voxel_of), _p(stats), _p(workspace),
-                               workspace.numel() * workspace.element_size(), _stream()), "g2v_voxel_assign")
+                               ws_bytes, _stream()), "g2v_voxel_assign")
     return voxel_of, stats.tolist()
 
 
@@ -1286,8 +1267,7 @@ def voxel_reduce(points, colors, voxel_of, M, voxel_size, origin, workspace=None
     origin; colors fp32 [N,3,H,W] -> (records uint8 [M,15] = <f4 x,y,z + u1 r,g,b, counts int32 [M], points fp32 [M,3], colors
     uint8 [M,3])."""
     N, H, W = _nhw3(points, "points")
-    assert colors.is_cuda and colors.dtype == torch.float32 and tuple(colors.shape) == (N, 3, H, W) and colors.is_contiguous(), \
-        "colors: fp32 [N,3,H,W], contiguous"
+    _colors_n3hw(colors, N, H, W)
     assert voxel_of.is_cuda and voxel_of.dtype == torch.int32 and tuple(voxel_of.shape) == (N, H, W) and voxel_of.is_contiguous(), \
         "voxel_of: int32 [N,H,W]"
     M = int(M)
@@ -1297,11 +1277,9 @@ def voxel_reduce(points, colors, voxel_of, M, voxel_size, origin, workspace=None
     counts = torch.empty(M, dtype=torch.int32, device=dev)
     out_points = torch.empty((M, 3), dtype=torch.float32, device=dev)
     out_colors = torch.empty((M, 3), dtype=torch.uint8, device=dev)
-    nbytes = voxel_reduce_workspace(M)
-    if workspace is None:
-        workspace = _cloud_workspace(nbytes, dev, "voxel_reduce")
+    workspace, ws_bytes = _workspace_arg(workspace, voxel_reduce_workspace(M), dev, "voxel_reduce")
     _ck(lib().g2v_voxel_reduce(_p(points), _p(colors), _p(voxel_of), N, H, W, float(voxel_size), ox, oy, oz, M, _p(records), _p(counts),
-                               _p(out_points), _p(out_colors), _p(workspace), workspace.numel() * workspace.element_size(), int(flags),
+                               _p(out_points), _p(out_colors), _p(workspace), ws_bytes, int(flags),
                                _stream()), "g2v_voxel_reduce")
     return records, counts, out_points, out_colors
 

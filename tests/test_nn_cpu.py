@@ -54,7 +54,7 @@ def test_library_exports_and_declares_the_entry_points(lib):
     assert [d.split()[-1] for d in decl.split(",")] == ["Nq", "Nt"] and hip._SIGS[q] == ([C.c_int64] * 2, C.c_int64)
     assert "nn.hip" in build.SOURCES and "nn.hip" not in build.RESOURCE_AUDIT
     assert re.search(r"#define G2V_NN_BRUTE 1\b", hdr) and re.search(r"#define G2V_NN_GRID 2\b", hdr) and (hip.NN_BRUTE, hip.NN_GRID) == (1, 2)
-    src = open(os.path.join(ROOT, "g2vlm_amd", "csrc", "nn.hip")).read()
+    src = open(os.path.join(ROOT, "g2vlm_amd", "csrc", "cloud_common.h")).read()   # sq_dist3: the rule's squared distance
     assert "#pragma clang fp contract(off)" in src
     for export in ("`nearest_points`", "`align_points`", "`evaluate_reconstruction`"):
         assert export in integration
