@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "lib", "libg2vlm_hip.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 SOURCES = ["gemm.hip", "gemm_big.hip", "gemm_8p.hip", "gemm_4w.hip", "gemm_skinny.hip", "attn.hip", "norm_rope.hip", "misc.hip", "decode.hip",
            "decode_layer.hip", "decode_batch.hip", "decode_shared.hip", "decode_fp8.hip", "decode_kv8.hip", "logprob.hip", "topk.hip", "cloud.hip",
-           "voxel.hip", "consistency.hip", "render.hip", "mesh.hip", "nn.hip"]
+           "voxel.hip", "consistency.hip", "render.hip", "mesh.hip", "nn.hip", "normals.hip"]
 
 
 # per-source flags.  attn.hip: hipcc's SLP vectoriser packs neighbouring f32 adds / multiplies of the softmax into v_pk_*_f32,

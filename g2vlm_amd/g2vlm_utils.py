@@ -442,24 +442,35 @@ def estimate_intrinsics(pred_dict, mask=None):
 
 
 # ---- triangle-mesh export (csrc/mesh.hip) ------------------------------------------------------------------------------------
+def _max_edge_arg(max_edge):
+    """max_edge as a float or None, or ValueError"""
+    if max_edge is None:
+        return None
+    try:
+        ok = not isinstance(max_edge, bool) and float(max_edge) >= 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"max_edge must be a number >= 0 (or None: no limit), got {max_edge!r}")
+    return float(max_edge)
+
+
+def _mask_replaces_filters(filters):
+    """ValueError if one of the filter arguments - (name, value, default) each - is given beside an explicit mask"""
+    given = [k for k, v, d in filters if not (v is d or v == d)]
+    if given:
+        raise ValueError(f"an explicit mask replaces the filters: {', '.join(given)} may not be given with it")
+
+
 def _mesh_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, filter_nan, min_views, max_in_front, depth_rtol, intrinsics, mask,
                  max_edge):
     """(points [N,H,W,3], images [N,3,H,W], mask uint8 [N,H,W], max_edge as a float or None) on the device, or ValueError: every
     check comes before any launch"""
-    if max_edge is not None:
-        try:
-            ok = not isinstance(max_edge, bool) and float(max_edge) >= 0.0
-        except (TypeError, ValueError):
-            ok = False
-        if not ok:
-            raise ValueError(f"max_edge must be a number >= 0 (or None: no limit), got {max_edge!r}")
-        max_edge = float(max_edge)
+    max_edge = _max_edge_arg(max_edge)
     if mask is not None:
-        given = [k for k, v, d in (("conf_threshold", conf_threshold, None), ("edge_rtol", edge_rtol, 0.03), ("edge_atol", edge_atol, None),
-                                   ("filter_nan", filter_nan, True), ("min_views", min_views, None), ("max_in_front", max_in_front, None),
-                                   ("depth_rtol", depth_rtol, 0.03), ("intrinsics", intrinsics, None)) if not (v is d or v == d)]
-        if given:
-            raise ValueError(f"an explicit mask replaces the filters: {', '.join(given)} may not be given with it")
+        _mask_replaces_filters((("conf_threshold", conf_threshold, None), ("edge_rtol", edge_rtol, 0.03), ("edge_atol", edge_atol, None),
+                                ("filter_nan", filter_nan, True), ("min_views", min_views, None), ("max_in_front", max_in_front, None),
+                                ("depth_rtol", depth_rtol, 0.03), ("intrinsics", intrinsics, None)))
     points, _, _, images, _ = _cloud_inputs(pred_dict, None, None, None, need_images=True)
     n, h, w = points.shape[:3]
     if n > 65535 or 2 * n * (h - 1) * (w - 1) > 2 ** 31 - 1:
@@ -506,6 +517,133 @@ def save_mesh(pred_dict, save_path, conf_threshold=None, edge_rtol=0.03, edge_at
     if verbose:
         print(f"{save_path}: {nv} vertices of {keep.numel()} pixels, {nf} triangles, per view {counts}")
     return dict(num_vertices=nv, num_faces=nf, counts=counts)
+
+
+# ---- surface normals (csrc/normals.hip) --------------------------------------------------------------------------------------
+def _view_angle_cos(max_view_angle):
+    """cos(max_view_angle) as the fp32 number the device compares with (fp64 cosine, rounded once), or ValueError"""
+    ok = isinstance(max_view_angle, (int, float, np.integer, np.floating)) and not isinstance(max_view_angle, bool)
+    a = float(max_view_angle) if ok else 0.0
+    if not (ok and 0.0 < a <= 90.0):
+        raise ValueError(f"max_view_angle must be an angle in degrees in (0, 90], got {max_view_angle!r}")
+    return float(np.float32(np.cos(np.radians(a))))
+
+
+def _normals_inputs(pred_dict, step, max_edge, frame, conf_threshold, edge_rtol, edge_atol, filter_nan, mask, need_images):
+    """(the points the normals are taken of [N,H,W,3], poses [N,4,4] or None, keep mask uint8 [N,H,W], images [N,3,H,W] or None, step,
+    max_edge as a float or None) on the device, or ValueError: every check comes before any launch"""
+    if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or not 1 <= step <= 8:
+        raise ValueError(f"step must be an integer in [1, 8], got {step!r}")
+    max_edge = _max_edge_arg(max_edge)
+    if frame not in ("world", "camera"):
+        raise ValueError(f"frame must be 'world' or 'camera', got {frame!r}")
+    if mask is not None:
+        _mask_replaces_filters((("conf_threshold", conf_threshold, None), ("edge_rtol", edge_rtol, 0.03), ("edge_atol", edge_atol, None),
+                                ("filter_nan", filter_nan, True)))
+        points, local, conf, images, logit = _cloud_inputs(pred_dict, None, None, None, need_images=need_images)
+    else:
+        points, local, conf, images, logit = _cloud_inputs(pred_dict, conf_threshold, edge_rtol, edge_atol, need_images=need_images)
+    n = points.shape[0]
+    if n > 65535:
+        raise ValueError(f"at most 65535 views per call, got {n}")
+    poses = None
+    if frame == "world":
+        poses = pred_dict.get("camera_poses")
+        if not torch.is_tensor(poses) or tuple(poses.shape) != (1, n, 4, 4):
+            raise ValueError(f"frame='world' needs pred_dict['camera_poses'] [1,N,4,4] with N = {n} (the normals look at each view's camera "
+                             f"centre), got {tuple(poses.shape) if torch.is_tensor(poses) else type(poses).__name__}")
+        poses = poses[0].detach().float().to(points.device).contiguous()
+    if mask is not None:
+        keep = _voxel_mask(mask, points.shape[:3], points.device)
+    else:
+        keep = _cloud_mask_u8(points, local, conf, logit, edge_rtol, edge_atol, filter_nan)
+    return (points if frame == "world" else local), poses, keep, images, int(step), max_edge
+
+
+def estimate_normals(pred_dict, step=1, max_edge=None, frame="world", conf_threshold=None, edge_rtol=0.03, edge_atol=None,
+                     filter_nan=True, mask=None, colors=False):
+    """A surface normal for every pixel of a recon result, on the device (hip.cloud_normals; include/g2vlm_hip.h and DESIGN.md 6u have
+    the exact rule): the cross products of the edges from a pixel's point to its four axis neighbours at distance `step`, summed over
+    the neighbour pairs that are there, normalised and turned towards the camera that saw the pixel - an image-space normal, no
+    plane fit over a larger window.  frame="world": normals of `points`, towards each view's centre in `camera_poses`;
+    frame="camera": normals of `local_points`, towards the origin.  The pixels that take part, as centres and as neighbours, are
+    those point_cloud_mask keeps under the same filter arguments (edge_rtol = 0.03 by default: no normal is taken across a depth
+    discontinuity); an explicit mask (bool / uint8 [N,H,W]) replaces the filters and may not be combined with them.  max_edge:
+    neighbours farther away than this (in the units of the points) do not count.
+    Returns, on the device, dict(normals fp32 [N,H,W,3] unit vectors, valid bool [N,H,W], cos_view fp32 [N,H,W] = the cosine of the
+    angle between the normal and the ray back to the camera, in [0, 1]); a pixel that takes no part, has no pair of neighbours or
+    whose neighbours are collinear is not valid and has zeros.  colors=True adds images fp32 [1,N,3,H,W] = n / 2 + 1 / 2, shaped like
+    pred_dict["images"]: dict(pred_dict, images=r["images"]) shows the normals through render_point_cloud and save_point_cloud_masked.
+    ValueError for every bad argument, before any launch."""
+    from . import hip
+    if not isinstance(colors, (bool, np.bool_)):
+        raise ValueError(f"colors must be a bool, got {colors!r}")
+    src, poses, keep, _, step, max_edge = _normals_inputs(pred_dict, step, max_edge, frame, conf_threshold, edge_rtol, edge_atol, filter_nan,
+                                                           mask, need_images=False)
+    r = hip.cloud_normals(src, keep, poses, step, max_edge, colors=bool(colors))
+    out = dict(normals=r["normals"], valid=r["valid"].view(torch.bool), cos_view=r["cos_view"])
+    if colors:
+        out["images"] = r["colors"].unsqueeze(0)
+    return out
+
+
+def view_angle_mask(pred_dict, max_view_angle, step=1, max_edge=None, frame="world", conf_threshold=None, edge_rtol=0.03, edge_atol=None,
+                    filter_nan=True, mask=None):
+    """Which pixels are seen at no more than max_view_angle degrees (in (0, 90]) from their surface normal: bool [N,H,W] on the
+    device.  A pixel is kept iff the filters (or the explicit mask) keep it, its normal is valid (estimate_normals, same arguments)
+    and cos_view >= float32(cos(max_view_angle)), the cosine taken in fp64 and rounded once.  Points seen at a grazing angle - where
+    a small error in the ray becomes a large error in depth - are what this drops."""
+    from . import hip
+    threshold = _view_angle_cos(max_view_angle)
+    src, poses, keep, _, step, max_edge = _normals_inputs(pred_dict, step, max_edge, frame, conf_threshold, edge_rtol, edge_atol, filter_nan,
+                                                           mask, need_images=False)
+    r = hip.cloud_normals(src, keep, poses, step, max_edge)
+    return (r["valid"] != 0) & (r["cos_view"] >= threshold)
+
+
+def save_point_cloud_normals(pred_dict, save_path, step=1, max_edge=None, max_view_angle=None, conf_threshold=None, edge_rtol=0.03,
+                             edge_atol=None, filter_nan=True, mask=None, verbose=True):
+    """save_point_cloud's PLY with `nx ny nz` beside every vertex (world frame; estimate_normals has the rule and the arguments), packed
+    on the device: mask, normals, stable compaction into 27-byte records <f4 x, y, z; <f4 nx, ny, nz; u1 r, g, b, ONE device-to-host
+    copy of the kept records, one write.  The vertices, their order and their colours are those of save_point_cloud_masked under the
+    same mask.  A kept pixel without a valid normal is written with a zero normal; max_view_angle (degrees, view_angle_mask) drops
+    such pixels along with those seen at a larger angle.  Returns dict(num_points, counts = kept pixels per view, num_normals = the
+    written vertices whose normal is valid)."""
+    from . import hip
+    threshold = None if max_view_angle is None else _view_angle_cos(max_view_angle)
+    points, poses, keep, images, step, max_edge = _normals_inputs(pred_dict, step, max_edge, "world", conf_threshold, edge_rtol, edge_atol,
+                                                                  filter_nan, mask, need_images=True)
+    r = hip.cloud_normals(points, keep, poses, step, max_edge)
+    if threshold is not None:
+        keep = ((r["valid"] != 0) & (r["cos_view"] >= threshold)).view(torch.uint8)
+    records, counts = hip.cloud_compact_normals(points, r["normals"], images, keep)
+    num_normals = int(((keep != 0) & (r["valid"] != 0)).sum().item())
+    os.makedirs(os.path.dirname(save_path) or ".", exist_ok=True)
+    host.write_ply_normal_records(save_path, records.cpu())
+    counts = counts.cpu().tolist()
+    if verbose:
+        print(f"{save_path}: {records.shape[0]} of {keep.numel()} points kept, {num_normals} with a normal, per view {counts}")
+    return dict(num_points=int(records.shape[0]), counts=counts, num_normals=num_normals)
+
+
+def save_normal_maps(pred_dict, directory, prefix="normal", frame="camera", step=1, max_edge=None, conf_threshold=None, edge_rtol=0.03,
+                     edge_atol=None, filter_nan=True, mask=None):
+    """estimate_normals' colours as PNGs directory/prefix_000.png ... (Pillow), one per view: the bytes the PLY export would write for
+    n / 2 + 1 / 2 - (uint8)(clip(c, 0, 1) * 255) -, black where no normal is valid.  frame="camera" by default: the usual normal map
+    beside a depth map (x right, y down, z forward; a wall that faces the camera has the normal (0, 0, -1) and the bytes
+    (127, 127, 0)).  Returns the paths."""
+    from PIL import Image
+    from . import hip
+    src, poses, keep, _, step, max_edge = _normals_inputs(pred_dict, step, max_edge, frame, conf_threshold, edge_rtol, edge_atol, filter_nan,
+                                                           mask, need_images=False)
+    colors = hip.cloud_normals(src, keep, poses, step, max_edge, colors=True)["colors"]
+    img = (colors.double().clamp(0.0, 1.0) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous().cpu().numpy()
+    os.makedirs(directory, exist_ok=True)
+    paths = []
+    for k, view in enumerate(img):
+        paths.append(os.path.join(directory, f"{prefix}_{k:03d}.png"))
+        Image.fromarray(view).save(paths[-1])
+    return paths
 
 
 # ---- evaluation against ground truth (csrc/nn.hip) ---------------------------------------------------------------------------

@@ -116,6 +116,9 @@ _SIGS = {
     "g2v_cloud_mesh": ([_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _L, _P, _P, _L, _P], C.c_int),
     "g2v_cloud_nn_workspace": ([_L, _L], C.c_int64),
     "g2v_cloud_nn": ([_P, _P, _L, _P, _P, _L, _F, _I, _P, _P, _P, _P, _L, _P], C.c_int),
+    "g2v_cloud_normals": ([_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P], C.c_int),
+    "g2v_cloud_compact_normals_workspace": ([_I, _I, _I], C.c_int64),
+    "g2v_cloud_compact_normals": ([_P, _P, _P, _P, _I, _I, _I, _P, _L, _P, _P, _L, _P], C.c_int),
     "g2v_voxel_bounds": ([_P, _P, _I, _I, _I, _P, _P], C.c_int),
     "g2v_voxel_assign_workspace": ([_I, _I, _I], C.c_int64),
     "g2v_voxel_assign": ([_P, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _L, _P], C.c_int),
@@ -1180,8 +1183,76 @@ def cloud_mesh(points, colors, mask, max_edge=None, faces=True, face_records=Tru
     return dict(vertex_records=vertex_records, faces=f, face_records=fr, used=used, vertex_of=vertex_of, counts=counts)
 
 
+# ------------------------------------------------------------------------------------------ surface normals (csrc/normals.hip)
+NORMALS_MAX_EDGE = 1                                        # G2V_NORMALS_MAX_EDGE
+NORMALS_PLAIN, NORMALS_HALO = 2, 4                          # G2V_NORMALS_PLAIN, G2V_NORMALS_HALO (A/B and tests only)
+NORMALS_STEP_MAX = 8                                        # G2V_NORMALS_STEP_MAX
+
+
+def cloud_normals_raw(points, mask, poses, step=1, max_edge=None, normals=None, valid=None, cos_view=None, colors=None, flags=0):
+    """One call of g2v_cloud_normals into the caller's tensors (no allocation, no host synchronisation): normals fp32 [N,H,W,3],
+    valid uint8 [N,H,W], cos_view fp32 [N,H,W], colors fp32 [N,3,H,W] where given - at least one.  flags: NORMALS_PLAIN /
+    NORMALS_HALO force a form of the kernel."""
+    N, H, W = _nhw3(points, "points")
+    mask = _mask_u8(mask, (N, H, W), optional=True)
+    if poses is not None:
+        assert poses.is_cuda and poses.dtype == torch.float32 and tuple(poses.shape) == (N, 4, 4) and poses.is_contiguous(), \
+            "poses: fp32 [N,4,4], contiguous"
+    assert normals is None or _nhw3(normals, "normals") == (N, H, W), "normals: the shape of points"
+    for t, dtype, what in ((valid, torch.uint8, "valid"), (cos_view, torch.float32, "cos_view")):
+        assert t is None or (t.is_cuda and t.dtype == dtype and tuple(t.shape) == (N, H, W) and t.is_contiguous()), f"{what}: {dtype} [N,H,W]"
+    if colors is not None:
+        _colors_n3hw(colors, N, H, W)
+    flags = int(flags) | (NORMALS_MAX_EDGE if max_edge is not None else 0)
+    _ck(lib().g2v_cloud_normals(_p(points), _p(mask), _p(poses), N, H, W, int(step), flags, float(max_edge or 0.0), _p(normals), _p(valid),
+                                _p(cos_view), _p(colors), _stream()), "g2v_cloud_normals")
+
+
+def cloud_normals(points, mask, poses, step=1, max_edge=None, colors=False):
+    """Image-space surface normals of recon's pointmaps (g2v_cloud_normals; include/g2vlm_hip.h has the exact rule): points fp32
+    [N,H,W,3], mask uint8 or bool [N,H,W] or None (all pixels), poses fp32 [N,4,4] camera-to-world or None (the camera at the origin:
+    camera-frame normals of local points), step = the distance to the four neighbours (1..8), max_edge = the longest edge to a
+    neighbour that counts (None: no limit).  Returns dict(normals fp32 [N,H,W,3] = unit vectors that look at the camera, valid uint8
+    [N,H,W], cos_view fp32 [N,H,W] = |cos| of the angle between the normal and the viewing ray, colors fp32 [N,3,H,W] = n / 2 + 1 / 2
+    or None); everything is 0 where valid is.  Bit-reproducible; no host synchronisation."""
+    N, H, W = _nhw3(points, "points")
+    dev = points.device
+    out = dict(normals=torch.empty((N, H, W, 3), dtype=torch.float32, device=dev), valid=torch.empty((N, H, W), dtype=torch.uint8, device=dev),
+               cos_view=torch.empty((N, H, W), dtype=torch.float32, device=dev),
+               colors=torch.empty((N, 3, H, W), dtype=torch.float32, device=dev) if colors else None)
+    cloud_normals_raw(points, mask, poses, step, max_edge, **out)
+    return out
+
+
+def cloud_compact_normals_workspace(N, H, W):
+    return int(lib().g2v_cloud_compact_normals_workspace(int(N), int(H), int(W)))
+
+
+def cloud_compact_normals(points, normals, colors, mask, workspace=None):
+    """The pixels mask keeps as packed 27-byte PLY records with normals (g2v_cloud_compact_normals): points, normals fp32 [N,H,W,3],
+    colors fp32 [N,3,H,W] in [0,1], mask uint8 or bool [N,H,W] -> (records uint8 [M,27] = <f4 x,y,z + <f4 nx,ny,nz + u1 r,g,b in
+    view-major, row-major order, counts int32 [N]).  Two calls: the first only counts, the records are then allocated at their exact
+    size and the second call fills them.  Synchronous: the counts are read back once."""
+    N, H, W = _nhw3(points, "points")
+    assert _nhw3(normals, "normals") == (N, H, W), "normals: the shape of points"
+    _colors_n3hw(colors, N, H, W)
+    mask = _mask_u8(mask, (N, H, W))
+    workspace, ws_bytes = _workspace_arg(workspace, cloud_compact_normals_workspace(N, H, W), points.device, "compact_normals")
+    counts = torch.empty(N, dtype=torch.int32, device=points.device)
+
+    def call(records, cap):
+        _ck(lib().g2v_cloud_compact_normals(_p(points), _p(normals), _p(colors), _p(mask), N, H, W, _p(records) if cap else None, cap,
+                                            _p(counts), _p(workspace), ws_bytes, _stream()), "g2v_cloud_compact_normals")
+    call(None, 0)
+    m = int(counts.sum(dtype=torch.int64).item())
+    records = torch.empty((m, 27), dtype=torch.uint8, device=points.device)
+    if m:
+        call(records, m)
+    return records, counts
+
+
 # ------------------------------------------------------------------------------------------ nearest neighbour (csrc/nn.hip)
-NN_BRUTE, NN_GRID = 1, 2                                    # G2V_NN_BRUTE, G2V_NN_GRID (A/B and tests only)
+NN_BRUTE, NN_GRID = 1, 2                                   # G2V_NN_BRUTE, G2V_NN_GRID (A/B and tests only)
 
 
 def cloud_nn_workspace(Nq, Nt):

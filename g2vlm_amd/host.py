@@ -360,6 +360,21 @@ def write_ply_records(path, records_u8):
         f.write(np.ascontiguousarray(rec).tobytes())
 
 
+def write_ply_normal_records(path, records_u8):
+    """write_ply_records for records with normals: uint8 [M, 27] (numpy or a host tensor), each <f4 x, y, z + <f4 nx, ny, nz +
+    u1 r, g, b as hip.cloud_compact_normals leaves them - the property order in which Open3D and MeshLab write a cloud with normals."""
+    rec = records_u8.numpy() if torch.is_tensor(records_u8) else np.asarray(records_u8)
+    if rec.dtype != np.uint8 or rec.ndim != 2 or rec.shape[1] != 27:
+        raise ValueError(f"write_ply_normal_records: uint8 [M, 27] expected, got {rec.dtype} {rec.shape}")
+    hdr = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {rec.shape[0]}\n"
+           "property float x\nproperty float y\nproperty float z\n"
+           "property float nx\nproperty float ny\nproperty float nz\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+    with open(path, "wb") as f:
+        f.write(hdr.encode("ascii"))
+        f.write(np.ascontiguousarray(rec).tobytes())
+
+
 def write_ply_mesh(path, vertex_records_u8, face_records_u8):
     """A triangle mesh as binary little-endian PLY from records that are packed already: vertices uint8 [V, 15] as for
     write_ply_records (and under its header text), faces uint8 [F, 13], each u1 3 + <i4 a, b, c as hip.cloud_mesh leaves them -

@@ -601,6 +601,52 @@ int64_t g2v_cloud_nn_workspace(int64_t Nq, int64_t Nt);
 int g2v_cloud_nn(const void* query, const void* query_mask, int64_t Nq, const void* target, const void* target_mask, int64_t Nt,
                  float max_distance, int flags, void* index, void* sq_distance, void* stats, void* workspace,
                  int64_t workspace_bytes, void* stream);
+
+/* ---- per-pixel surface normals (csrc/normals.hip): image-space normals of every view's pixel grid ---------------------------
+ * points fp32 [N,H,W,3], mask u8 [N,H,W] or NULL (all pixels), poses fp32 [N,4,4] camera-to-world or NULL (the camera of every
+ * view is at the origin: camera-frame normals of local points), step 1..G2V_NORMALS_STEP_MAX = the distance to the neighbours,
+ * max_edge fp32, read only with G2V_NORMALS_MAX_EDGE in flags.
+ *
+ * The rule is exact: fp32 throughout, every - * + rounded once, no fused multiply-add, sqrt and / correctly rounded, every
+ * comparison an IEEE compare (false on NaN).  Pixel P = (y, x) of view i takes part iff mask != 0 (or mask is NULL) and its
+ * three coordinates are finite.  Its neighbours are R = (y, x+step), D = (y+step, x), L = (y, x-step), U = (y-step, x).  A
+ * neighbour Q is available iff it lies inside the same view, takes part and, with G2V_NORMALS_MAX_EDGE, its edge e = Q - P has
+ * (e0 e0 + e1 e1) + e2 e2 <= max_edge max_edge (the product formed once in fp32; equality is kept, an edge with a NaN fails).
+ * For the pairs (a, b) = (R,D), (D,L), (L,U), (U,R), in this order, of which both edges are available:
+ *   c0 = a1 b2 - a2 b1,  c1 = a2 b0 - a0 b2,  c2 = a0 b1 - a1 b0   (each product rounded, then the difference);
+ * m = the sum of the present c in that order, starting from the first present one (not from +0);
+ * s2 = (m0 m0 + m1 m1) + m2 m2.  The pixel is VALID iff it takes part, at least one pair is present, s2 is finite and s2 > 0.
+ * If valid:  n = m / sqrt(s2) (three divisions);  d = P - C with C = (pose[3], pose[7], pose[11]) of view i, or 0 without poses;
+ *   t = (n0 d0 + n1 d1) + n2 d2;  if t > 0 the sign bit of all three components of n is flipped (the normal looks at the camera;
+ *   -0.0 can occur);  dd = (d0 d0 + d1 d1) + d2 d2;  q = |t| / sqrt(dd), a NaN q replaced by 0;  cos_view = min(q, 1);
+ *   colour k = n_k * 0.5f + 0.5f (two roundings).
+ * If not valid every output is +0.0 / 0.
+ *
+ * Outputs, each optional (NULL) but not all four at once: normals fp32 [N,H,W,3], valid u8 [N,H,W], cos_view fp32 [N,H,W],
+ * colors_out fp32 [N,3,H,W] (the layout of `colors` / images).  The result depends on nothing but the inputs: no atomics, the
+ * same bytes on every run.  G2V_NORMALS_PLAIN / G2V_NORMALS_HALO (A/B and tests only) force a form of the kernel: the neighbours
+ * by plain global loads, or - step 1 only - from a tile with a one-pixel halo staged in LDS.  The bytes are the same; without a
+ * flag the plain form runs.
+ * -22 before any launch for a dimension <= 0, N H W above 2^31 - 1, N > 65535, a step outside [1, G2V_NORMALS_STEP_MAX], an unknown
+ * flag, both form flags, G2V_NORMALS_HALO with step != 1, a max_edge that is negative or NaN with the flag set, points NULL, all
+ * four outputs NULL and an fp32 pointer that is not 4-byte aligned.  One launch, no workspace; hipGraph-capturable.
+ *
+ * g2v_cloud_compact_normals is g2v_cloud_compact for 27-byte records <f4 x, y, z; <f4 nx, ny, nz; u1 r, g, b (the property order
+ * that Open3D and MeshLab write): the pixels with mask != 0 in view-major, row-major order, the normal copied bit for bit from
+ * normals fp32 [N,H,W,3], the colour bytes those of g2v_cloud_compact; counts int32 [N] = the kept pixels of every view, always
+ * their true numbers; records past max_records are not written (0, with records NULL, only counts).  The workspace
+ * (8 N ceil(H W / 1024) bytes, no initialisation needed) and the -22 cases are g2v_cloud_compact's, plus normals NULL; the query
+ * returns 0 for every shape that the entry point refuses.  Three launches; hipGraph-capturable.  */
+#define G2V_NORMALS_MAX_EDGE 1
+#define G2V_NORMALS_PLAIN 2
+#define G2V_NORMALS_HALO 4
+#define G2V_NORMALS_STEP_MAX 8
+int g2v_cloud_normals(const void* points, const void* mask, const void* poses, int N, int H, int W, int step, int flags,
+                      float max_edge, void* normals, void* valid, void* cos_view, void* colors_out, void* stream);
+int64_t g2v_cloud_compact_normals_workspace(int N, int H, int W);
+int g2v_cloud_compact_normals(const void* points, const void* normals, const void* colors, const void* mask, int N, int H, int W,
+                              void* records, int64_t max_records, void* counts, void* workspace, int64_t workspace_bytes,
+                              void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -11,7 +11,10 @@ matrix per view; --voxel-size (with --voxel-min-points) voxel-downsamples the cl
 with an edge longer than L); --evaluate GT.npy measures the reconstruction against a ground-truth cloud (evaluate_reconstruction, under
 the filters given: a [N,H,W,3] array pixel-aligned with the views, or an unordered [M,3] cloud with --eval-align none) and prints
 accuracy, completeness, Chamfer distance and precision / recall / F-score at every --eval-threshold T; --eval-max-distance D clips
-the search, --eval-align sim3|none picks the alignment."""
+the search, --eval-align sim3|none picks the alignment; --normals-ply PATH also writes the cloud with a surface normal per vertex
+(save_point_cloud_normals, under the filters given) and --normal-maps DIR one normal-map PNG per view (save_normal_maps), with
+--normal-step S the distance to the neighbours a normal is taken from (1..8), --normal-max-edge L the longest edge to a neighbour that
+counts and --max-view-angle DEG (--normals-ply only) dropping the points seen at more than DEG degrees from their normal."""
 import argparse
 import os
 import sys
@@ -54,6 +57,48 @@ parser.add_argument("--eval-max-distance", type=float, default=None, metavar="D"
                     help="with --evaluate: neighbours farther than D do not count (such points are misses, and enter the means with D)")
 parser.add_argument("--eval-align", type=str, default=None, choices=("sim3", "none"),
                     help="with --evaluate: fit a similarity on the pixels valid on both sides (default for [N,H,W,3]) or compare as is")
+
+
+parser.add_argument("--normals-ply", type=str, default=None, metavar="PATH",
+                    help="also write the cloud with a surface normal per vertex (binary PLY with nx ny nz)")
+parser.add_argument("--normal-maps", type=str, default=None, metavar="DIR", help="write normal_000.png ...: a camera-frame normal map per input view")
+parser.add_argument("--normal-step", type=int, default=None, metavar="S",
+                    help="with --normals-ply / --normal-maps: the distance in pixels to the neighbours a normal is taken from (1..8, default 1)")
+parser.add_argument("--normal-max-edge", type=float, default=None, metavar="L",
+                    help="with --normals-ply / --normal-maps: neighbours farther than L from the pixel's point do not count")
+parser.add_argument("--max-view-angle", type=float, default=None, metavar="DEG",
+                    help="with --normals-ply: drop points seen at more than DEG degrees from their normal, in (0, 90]")
+
+
+def check_normal_flags(args):
+    """refuses --normal-step / --normal-max-edge / --max-view-angle without an output that uses them, and values out of range"""
+    if args.normals_ply is None and args.normal_maps is None:
+        if args.normal_step is not None or args.normal_max_edge is not None or args.max_view_angle is not None:
+            parser.error("--normal-step, --normal-max-edge and --max-view-angle need --normals-ply PATH or --normal-maps DIR")
+    if args.normal_step is not None and not 1 <= args.normal_step <= 8:
+        parser.error("--normal-step S must be in 1..8")
+    if args.normal_max_edge is not None and not args.normal_max_edge >= 0:
+        parser.error("--normal-max-edge L must be >= 0")
+    if args.max_view_angle is not None and (args.normals_ply is None or not 0 < args.max_view_angle <= 90):
+        parser.error("--max-view-angle DEG needs --normals-ply and DEG in (0, 90]")
+
+
+def write_normals(pred, args):
+    """--normals-ply / --normal-maps: under the filters given on the command line; with no filter flag at all, the functions' defaults
+    (edge_rtol = 0.03)"""
+    from g2vlm_utils import point_cloud_mask, save_normal_maps, save_point_cloud_normals
+    kw = dict(step=args.normal_step or 1, max_edge=args.normal_max_edge)
+    if args.min_views is not None or args.max_in_front is not None or args.edge_rtol is not None or args.edge_atol is not None \
+            or args.conf_threshold is not None:
+        consistency = {}
+        if args.min_views is not None or args.max_in_front is not None:
+            consistency = dict(min_views=args.min_views, max_in_front=args.max_in_front, depth_rtol=args.consistency_rtol)
+        kw["mask"] = point_cloud_mask(pred, conf_threshold=args.conf_threshold, edge_rtol=args.edge_rtol, edge_atol=args.edge_atol, **consistency)
+    if args.normals_ply is not None:
+        save_point_cloud_normals(pred, args.normals_ply, max_view_angle=args.max_view_angle, **kw)
+    if args.normal_maps is not None:
+        paths = save_normal_maps(pred, args.normal_maps, **kw)
+        print(f"{args.normal_maps}: {len(paths)} normal maps")
 
 
 def check_evaluation_flags(args):
@@ -136,8 +181,9 @@ def main(argv=None):
         parser.error("--render-radius must be in 0..8")
     if args.mesh_max_edge is not None and (args.mesh is None or not args.mesh_max_edge >= 0):
         parser.error("--mesh-max-edge L needs --mesh and L >= 0")
+    check_normal_flags(args)
     gt = check_evaluation_flags(args)
-    names = sorted(n for n in os.listdir(args.image_folder) if n.lower().endswith((".png", ".jpg", ".jpeg")))
+    names =sorted(n for n in os.listdir(args.image_folder) if n.lower().endswith((".png", ".jpg", ".jpeg")))
     image_names = [os.path.join(args.image_folder, n) for n in names]
     print(image_names)
     model, tokenizer, new_token_ids, vit_image_transform, dino_transform = load_model_and_tokenizer(args.model_path)
@@ -158,6 +204,8 @@ def main(argv=None):
         render_views(pred, args)
     if args.mesh is not None:
         write_mesh(pred, args)
+    if args.normals_ply is not None or args.normal_maps is not None:
+        write_normals(pred, args)
     if gt is not None:
         pred["evaluation"] = evaluate(pred, args, gt)
     if args.intrinsics:
