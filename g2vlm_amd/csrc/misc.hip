@@ -380,8 +380,13 @@ __global__ __launch_bounds__(256) void argmax_bf16_kernel(const __bf16* x, int n
     const float inv_t = __int_as_float(rng[3]);
     for (int i = lo + threadIdx.x; i < hi; i += 256) {
       const uint32_t r = philox_first((uint32_t)i, blockIdx.y, step, 0u, k0, k1);
-      const float u = ((float)(r >> 8) + 0.5f) * (1.0f / 16777216.0f);          // 24 bits, strictly inside (0, 1)
-      argmax_merge(best, bi, argmax_key(bf2f(x[i]) * inv_t - logf(-logf(u))), i);
+      // u = (r24 + 0.5) / 2^24, strictly inside (0, 1).  fp32 holds r24 + 0.5 only below 2^23: above, the sum rounds to an integer
+      // (r24 = 2^24 - 1 gave u = 1, a score of +inf - a uniformly random token once per 2^24 elements - and the draws that win, all
+      // near u = 1, lost up to half a step of 1 - u).  There 1 - u = (2^24 - r24 - 0.5) / 2^24 is exact, and -log u = -log1p(-(1 - u)).
+      const uint32_t r24 = r >> 8;
+      const float nlu = r24 < (1u << 23) ? -logf(((float)r24 + 0.5f) * (1.0f / 16777216.0f))
+                                         : -log1pf(-(((float)(0xFFFFFFu - r24) + 0.5f) * (1.0f / 16777216.0f)));
+      argmax_merge(best, bi, argmax_key(bf2f(x[i]) * inv_t - logf(nlu)), i);
     }
   } else {
     for (int i = lo + threadIdx.x; i < hi; i += 256) argmax_merge(best, bi, argmax_key(bf2f(x[i])), i);
